@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark: charon's BLS hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run builds the C2 inputs, warms up, times K steps, writes the last step's outputs if --dump-outputs is given
+(the same seeded inputs on every run, so two builds compare output for output) and prints the line.  --full adds
+every other measurement after the steps: C3, C4, C5, the pubshare-table and host-buffer paths, the n = 1 latency
+and the CPU baseline, as extra fields of the same line.
 
 Step = one pass of the hot path over one batch: tbls.Verify of the configs[1] workload (C2:
 65,536 partial signatures over distinct 32-byte signing roots, 1% corrupted) through the C-ABI
 device entry point, inputs already resident in HBM.  Multi-GPU is weak scaling: every rank owns its
-own validator-index shard of the same size (no data-path collective).  Threshold aggregation (C3:
-10,000 validators x 7-of-10 + Verify of each aggregate) is timed after the main loop and reported as
+own validator-index shard of the same size (no data-path collective).  With --full, threshold aggregation
+(C3: 10,000 validators x 7-of-10 + Verify of each aggregate) is timed after the main loop and reported as
 an extra field.  Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -88,7 +93,17 @@ def parse():
     ap.add_argument("--latency-calls", type=int, default=1000,
                     help="synchronous n = 1 tbls.Verify calls (hipbls_verify on an idle queue) timed one after another, "
                          "the unpatched parsigex loop's shape (0 = skip; rank 0 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the C2 steps also run every other measurement and check (C3, C4, C5, the pubshare-table "
+                         "and host-buffer paths, the n = 1 latency, the CPU baseline), each sized by its own option "
+                         "above; without it only the C2 steps run and those options are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned to its caller as DIR/<name>.npy")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the C2 steps, print the line
+        args.tagg_groups = args.cpu_sample = args.rlc_node_validators = args.latency_calls = 0
+        args.c5 = args.keys = args.host_path = 0
+    return args
 
 
 def log(*a):
@@ -350,6 +365,23 @@ def cpu_baseline(impl, c2, n_sample, rng):
                             "threshold_aggregates_per_s": round(G / t_agg, 1)}}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array of `arrays` (name -> array) as <directory>/<name>.npy in float32 (statuses and bitmap
+    bits are small integers, exact in float32).  All files together stay under DUMP_MAX_BYTES: a larger array is cut to
+    a fixed sample, the same sorted seeded indices on every run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (4 * max(1, len(arrays))) - 64  # elements per file, the .npy header allowed for
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.RandomState(SEED & 0xFFFFFFFF).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float32))
+
+
 def timed_loop(step, steps, dev, barrier, world):
     """barrier + synchronize, `steps` calls, synchronize + barrier; max over ranks (seconds)."""
     import torch
@@ -468,6 +500,11 @@ def main():
     lib.hipbls_kernel_timing_reset()
     elapsed = timed_loop(step, args.steps, dev, barrier, world)
     st = d_st.cpu().tolist()
+    if args.dump_outputs and rank == 0:  # what the last timed step handed back, before anything judges it
+        outs = {"verify_status": st}  # this rank's slice: one hipbls status per item, 0 = verified
+        if world > 1 and node_ok[0] is not None:
+            outs["node_bitmap"] = node_ok[0].cpu().numpy()  # the gathered node batch: 1 = verified
+        dump_outputs(args.dump_outputs, outs)
     assert {i for i, s in enumerate(st) if s != 0} == bad, "verify bitmap mismatch"
     if world > 1:  # the gathered node bitmap equals the node batch's construction
         want = {i for i in range(n_node) if c2_is_bad(i)[0]}
@@ -981,6 +1018,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(1000 * elapsed / args.steps, 3),
             "higher_is_better": True,
             "scaling": "weak",

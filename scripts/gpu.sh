@@ -4,8 +4,8 @@
 #
 #   suite                 the whole GPU test suite                         -> gpurun_out/<tag>_suite.log
 #   smoke                 __graft_entry__.smoke()                          -> gpurun_out/<tag>_smoke.log
-#   bench                 the default bench line                           -> gpurun_out/<tag>_bench.json
-#   prof                  the default bench under rocprofv3 --kernel-trace --stats -> gpurun_out/<tag>_prof/
+#   bench                 the whole bench line (bench.py --full)           -> <out>/<tag>_bench.json
+#   prof                  bench.py --full under rocprofv3 --kernel-trace --stats -> <out>/<tag>_prof/
 #   rlc:<lib>:<name>      the C4(i) + C5 part of the bench with HIPBLS_LIB=<lib> (A/B of compile-time variants)
 #   c2:<lib>:<name>       the C2 part of the bench alone (5 steps) with HIPBLS_LIB=<lib>; repeat the step to alternate
 #   c3:<lib>:<name>       the C3 part (sigagg, 6 timed calls) with a 4,096-item C2, HIPBLS_LIB=<lib>
@@ -22,9 +22,9 @@ T=${TAG:-run}
 mkdir -p "$O"
 cd "$R" || exit 1
 export TMPDIR=/tmp
-RLC_ARGS="--steps 2 --warmup 1 --tagg-groups 0 --latency-calls 0 --host-path 0 --keys 0 --cpu-sample 0 --rlc-steps 3 --rlc-variants i"
+RLC_ARGS="--full --steps 2 --warmup 1 --tagg-groups 0 --latency-calls 0 --host-path 0 --keys 0 --cpu-sample 0 --rlc-steps 3 --rlc-variants i"
 C2_ONLY="--tagg-groups 0 --latency-calls 0 --host-path 0 --keys 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0"
-C3_ONLY="--c2-items 4096 --steps 2 --warmup 1 --tagg-steps 6 --latency-calls 0 --host-path 0 --keys 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0"
+C3_ONLY="--full --c2-items 4096 --steps 2 --warmup 1 --tagg-steps 6 --latency-calls 0 --host-path 0 --keys 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0"
 C2_ARGS="--steps 3 --warmup 1 --tagg-groups 0 --latency-calls 0 --host-path 0 --keys 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0"
 
 for step in "$@"; do
@@ -39,13 +39,13 @@ for step in "$@"; do
         || { echo "smoke failed"; tail -20 "$O/${T}_smoke.log"; exit 1; }
       tail -1 "$O/${T}_smoke.log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$O/${T}_bench.json" 2> "$O/${T}_bench.err" \
+      timeout -k 10 600 python -u bench.py --full > "$O/${T}_bench.json" 2> "$O/${T}_bench.err" \
         || { echo "bench failed"; tail -30 "$O/${T}_bench.err"; exit 1; }
       python3 scripts/bench_summary.py "$O/${T}_bench.json" ;;
     prof)
       mkdir -p "$O/${T}_prof"
       (cd /tmp && timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${T}_prof" -o run \
-        -- python3 -u "$R/bench.py" > "$O/${T}_prof_bench.json" 2> "$O/${T}_prof_bench.err") \
+        -- python3 -u "$R/bench.py" --full > "$O/${T}_prof_bench.json" 2> "$O/${T}_prof_bench.err") \
         || { echo "profiled bench failed"; tail -30 "$O/${T}_prof_bench.err"; exit 1; }
       python3 scripts/bench_summary.py "$O/${T}_prof_bench.json" ;;
     rlc:*)

@@ -10,10 +10,10 @@ O=$R/gpurun_out/${PREFIX:-pmc6_}$WL
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 case $WL in
-  lat) ARGS="--c2-items 8192 --steps 1 --warmup 0 --tagg-groups 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0 --keys 0 --host-path 0 --latency-calls 40";;
+  lat) ARGS="--full --c2-items 8192 --steps 1 --warmup 0 --tagg-groups 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0 --keys 0 --host-path 0 --latency-calls 40";;
   c2) ARGS="--steps 1 --warmup 0 --tagg-groups 0 --cpu-sample 0 --rlc-node-validators 0 --c5 0 --keys 0 --host-path 0 --latency-calls 0";;
-  c3) ARGS="--c2-items 40960 --steps 1 --warmup 0 --tagg-steps 1 --cpu-sample 0 --rlc-node-validators 0 --c5 0 --keys 0 --host-path 0 --latency-calls 0";;
-  c4) ARGS="--c2-items 40960 --steps 1 --warmup 0 --tagg-groups 0 --rlc-steps 1 --rlc-variants i,all_valid,ii_all_valid --c5 0 --keys 0 --host-path 0 --latency-calls 0 --cpu-sample 0";;
+  c3) ARGS="--full --c2-items 40960 --steps 1 --warmup 0 --tagg-steps 1 --cpu-sample 0 --rlc-node-validators 0 --c5 0 --keys 0 --host-path 0 --latency-calls 0";;
+  c4) ARGS="--full --c2-items 40960 --steps 1 --warmup 0 --tagg-groups 0 --rlc-steps 1 --rlc-variants i,all_valid,ii_all_valid --c5 0 --keys 0 --host-path 0 --latency-calls 0 --cpu-sample 0";;
   *) echo "unknown WL $WL"; exit 2;;
 esac
 i=0
