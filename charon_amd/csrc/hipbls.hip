@@ -73,12 +73,19 @@ __global__ void k_g1m_miller8(uint64_t nl_max, const uint32_t* meta, const uint3
                               uint64_t fstride);
 __global__ void k_fav_prep8(const uint8_t* pks, uint64_t nkeys, const uint8_t* sigs, const uint8_t* msgs,
                             const uint64_t* moffs, uint64_t G, uint32_t* pts, int32_t* kcode, uint32_t* ws);
+__global__ void k_tv_prep8(const uint8_t* pks, const uint8_t* msgs, const uint64_t* moffs, uint64_t G,
+                           const int64_t* ids, const uint64_t* goffs, uint32_t* ws, int32_t* vstatus,
+                           const uint8_t* sigs, uint64_t n_parts, uint32_t* pts, int32_t* pstat, uint32_t with_keys);
+__global__ void k_tagg_sum8(const uint32_t* pts, const int32_t* pstat, const int64_t* ids, const uint64_t* goffs,
+                            uint64_t n_parts, uint8_t* out, int32_t* status);
 }  // namespace bls_fp2p
 // The sixteen-lane check for batches of at most four items (verify_hex.hip: BLS_FP2_PAIR + BLS_HEX, namespace bls_hex).
 namespace bls_hex {
 __global__ void k_verify_pair_lq16(const uint32_t* ws, uint64_t n, int32_t* status, uint32_t replicas, uint32_t* race,
                                    uint32_t epoch);
-
+__global__ void k_tv_pair_lq16(const uint32_t* pts, const int32_t* pstat, const int64_t* ids, const uint64_t* goffs,
+                               uint64_t G, uint64_t n_parts, const uint32_t* ws, int32_t* astatus, int32_t* vstatus,
+                               uint8_t* out);
 }  // namespace bls_hex
 // FastAggregateVerify's check at two waves per SIMD (fav_wide.hip: verify_hex.hip again, namespace bls_hexw).
 namespace bls_hexw {
@@ -360,6 +367,7 @@ const KernelRef kKernels[] = {
     KREF(k_verify_pair_single), KREF(k_verify_prep), KREF(k_zero_sig_status), KREF8(k_g1m_miller8),
     KREF8(k_rlcb_final8), KREF8(k_rlcb_sfactor8), KREF8(k_verify_pair_lq8), KREF8(k_verify_prep8),
     KREF16(k_verify_pair_lq16), KREF8(k_fav_prep8), KREF16W(k_fav_pair_lq16),
+    KREF8(k_tv_prep8), KREF8(k_tagg_sum8), KREF16(k_tv_pair_lq16),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -1464,6 +1472,24 @@ int launch_rlc_batch(Context& c, const uint8_t* d_pks, const uint8_t* d_sigs, co
   return ws_end(c, s, WS_RLC);
 }
 
+// A lone sigagg call (one proposer duty: core/sigagg/sigagg.go:138-159 with one validator, at most a few) takes the
+// drop-in path's layouts instead of one lane per unit of work: the root keys, the hashes and the partials on octets
+// (verify_lat.hip k_tv_prep8), then per group the sum, the sixteen-lane check and [L^-1] S (verify_hex.hip
+// k_tv_pair_lq16; k_tagg_sum8 for the aggregate-only call).  The _device entry points know only the two counts on the
+// host, so the kernels hold for any split of at most 64 partials over at most 4 groups.  AUTO pair mode only, so the
+// forced modes keep the throughput kernels for the layout-parity tests; HIPBLS_LAT_HEX=0 turns it off with the other
+// sixteen-lane paths, HIPBLS_LAT_SIGAGG=0 alone.
+constexpr uint64_t kTaggLatMaxGroups = 4, kTaggLatMaxParts = 64;
+bool initial_lat_sigagg() {
+  const char* e = getenv("HIPBLS_LAT_SIGAGG");
+  return !(e && e[0] == '0');
+}
+const bool g_lat_sigagg = initial_lat_sigagg();
+bool use_tagg_lat(uint64_t n_groups, uint64_t n_parts) {
+  return g_lat_hex && g_lat_sigagg && g_pair_mode.load() == HIPBLS_PAIR_AUTO && n_groups <= kTaggLatMaxGroups &&
+         n_parts <= kTaggLatMaxParts;
+}
+
 int launch_tagg(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const uint64_t* d_goffs, uint64_t n_groups,
                 uint64_t n_parts, uint8_t* d_out, int32_t* d_status, hipStream_t s) {
   if (n_groups == 0) return HIPBLS_OK;
@@ -1471,6 +1497,24 @@ int launch_tagg(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const u
   HIP_TRY(c.b_pst.ensure((n_parts ? n_parts : 1) * 4));
   int rc = ws_begin(c, s);
   if (rc) return rc;
+  if (use_tagg_lat(n_groups, n_parts)) {
+    if (n_parts) {
+      rc = timed(c, "tv_prep8", s, [&] {
+        hipLaunchKernelGGL(bls_fp2p::k_tv_prep8, dim3((unsigned)((8 * n_parts + kBlock - 1) / kBlock)), dim3(kBlock),
+                           0, s, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (const uint64_t*)nullptr, n_groups,
+                           d_ids, d_goffs, (uint32_t*)nullptr, (int32_t*)nullptr, d_sigs, n_parts,
+                           (uint32_t*)c.b_pts.p, (int32_t*)c.b_pst.p, 0u);
+      });
+      if (rc) return rc;
+    }
+    rc = timed(c, "tagg_sum8", s, [&] {
+      hipLaunchKernelGGL(bls_fp2p::k_tagg_sum8, dim3((unsigned)n_groups), dim3(kBlock), 0, s,
+                         (const uint32_t*)c.b_pts.p, (const int32_t*)c.b_pst.p, d_ids, d_goffs, n_parts, d_out,
+                         d_status);
+    });
+    if (rc) return rc;
+    return ws_end(c, s);
+  }
   if (n_parts) {
     rc = timed(c, "tagg_scale", s, [&] {
       hipLaunchKernelGGL(k_tagg_scale, dim3((unsigned)grid_for(n_parts)), dim3(kBlock), 0, s, d_sigs, d_ids, d_goffs,
@@ -1529,6 +1573,22 @@ int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, 
   // wave slots, while this call's phase A beside the previous call's check fills the SIMDs that check leaves idle.
   HIP_TRY(hipStreamWaitEvent(s, c.tv_phase, 0));
   int rc = HIPBLS_OK;
+  if (use_tagg_lat(n_groups, n_parts)) {
+    // the kernel derives the same role boundaries from n_groups and n_parts
+    const uint64_t nbg = (8 * n_groups + kBlock - 1) / kBlock, nbp = (8 * n_parts + kBlock - 1) / kBlock;
+    rc = timed(c, "tv_prep8", s, [&] {
+      hipLaunchKernelGGL(bls_fp2p::k_tv_prep8, dim3((unsigned)(2 * nbg + nbp)), dim3(kBlock), 0, s, d_dvpks, d_msgs,
+                         d_moffs, n_groups, d_ids, d_goffs, ws, d_vstatus, d_sigs, n_parts, pts, pst, 1u);
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c.tv_phase, s));
+    tv_end.phase = true;
+    return timed(c, "tv_lq16", s, [&] {
+      hipLaunchKernelGGL(bls_hex::k_tv_pair_lq16, dim3((unsigned)(2 * n_groups)), dim3(kBlock), 0, s,
+                         (const uint32_t*)pts, (const int32_t*)pst, d_ids, d_goffs, n_groups, n_parts,
+                         (const uint32_t*)ws, d_astatus, d_vstatus, d_out);
+    });  // tv_end records tv_done[p]
+  }
   if (BLS_TV_PAIR_HASH && n_groups <= kPairHashMaxVerify) {
     const uint64_t nprep = 3 * grid_for(n_groups), nscale = n_parts ? grid_for(n_parts) : 0;
     rc = timed(c, "tv_phase_a", s, [&] {

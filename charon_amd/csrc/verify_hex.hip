@@ -23,6 +23,9 @@
 #include "race.h"
 
 #include "lg2.h"
+#ifndef BLS_HEX_FAV_WIDE
+#include "tagg_lat.h"
+#endif
 
 namespace bls {
 
@@ -62,6 +65,50 @@ __global__ void __launch_bounds__(kHexBlock) k_verify_pair_lq16(const uint32_t* 
   st = lq4_verify(pk, hm, sig, (int)(t & 3));
   if (lead) status[i] = st;
   bls_race::finish();
+}
+
+// The lone sigagg route's stage 2 (hipbls.hip launch_tagg_verify, at most 4 groups; verify_lat.hip k_tv_prep8 is
+// stage 1), two workgroups per group g, roles uniform per workgroup.  Both compose the group's status and sum its
+// scaled partials into S (tagg_lat.h tagg_sum_octet: k_tagg_sum_s's order).  Workgroups [0, G), lanes 0-15: the join
+// (kernels.h k_tv_join: an aggregation failure overrides the key's status, S at infinity is "not verified") and
+// lq4_verify([L] pk, H(m), S) in the sixteen-lane layout; they write both statuses.  Workgroups [G, 2 G), lanes 0-7:
+// sigma = [L^-1] S compressed into out (tagg_unscale_octet), beside the check on another CU, so the 96 bytes cost the
+// call nothing.  Neither role reads what the other writes.  Not raced.
+__global__ void __launch_bounds__(kHexBlock) k_tv_pair_lq16(const uint32_t* __restrict__ pts,
+                                                            const int32_t* __restrict__ pstat,
+                                                            const int64_t* __restrict__ ids,
+                                                            const uint64_t* __restrict__ goffs, uint64_t G,
+                                                            uint64_t n_parts, const uint32_t* __restrict__ ws,
+                                                            int32_t* __restrict__ astatus,
+                                                            int32_t* __restrict__ vstatus, uint8_t* __restrict__ out) {
+  bls_race::init(nullptr, 0u);
+  const int tid = threadIdx.x;
+  const bool unscale = blockIdx.x >= G;  // uniform per workgroup
+  const uint64_t g = unscale ? blockIdx.x - G : blockIdx.x;
+  if (tid >= (unscale ? 8 : 16)) return;
+  g2j S;
+  const int ast = tagg_sum_octet(S, pts, pstat, goffs, g, n_parts, tid & 3);
+  if (unscale) {
+    tagg_unscale_octet(S, ast, g, ids, goffs, out, tid & 3, tid == 0);
+    return;
+  }
+  int st = vstatus[g];  // the key's: ERR_PUBKEY, ERR_VERIFY (identity) or pending
+  if (ast != HIPBLS_OK)
+    st = ast;
+  else if (st == RLC_PENDING && jac_is_inf(S))
+    st = HIPBLS_ERR_VERIFY;
+  if (st == RLC_PENDING) {  // the same on all sixteen lanes
+    g1a pk;
+    g2a hm, sig;
+    soa_load<24>(&pk.x.v[0], ws, G, g);
+    soa_load<48>(&hm.x.c0.v[0], ws + 24 * G, G, g);
+    jac_to_aff(sig, S);
+    st = lq4_verify(pk, hm, sig, tid & 3);
+  }
+  if (tid == 0) {
+    astatus[g] = ast;
+    vstatus[g] = st;
+  }
 }
 
 #else

@@ -20,110 +20,14 @@
 
 #include "lg2.h"
 #include "rlcb.h"
+#include "tagg_lat.h"
 
 namespace bls {
 
 constexpr int kOctBlock = 64;
 
 // ---------------------------------------------------------------- the hash's cofactor clearing on a lane quad
-// G2 doubling (curve.h jac_dbl_body, dbl-2009-l) with its seven Fp2 products dealt out over the quad's lanes
-// (q = lane & 3): level 1 X^2 | Y^2 | Y Z, level 2 B^2 | (X + B)^2 | E^2, level 3 E (D - X3) on every lane; each level's
-// products are broadcast to the quad (lg2.h quad_bcast).  Three products of latency instead of seven; every lane
-// ends with the same point.  All four lanes (and, here, their Fp2 twins) must be active.
-__device__ __forceinline__ void g2_dbl_quad(g2j& r, const g2j& p, int q) {
-  const uint32_t q1 = q == 1 ? ~0u : 0u, q2 = q == 2 ? ~0u : 0u;
-  fp2 x, y, o;
-  x = sel(q2, p.y, sel(q1, p.y, p.x));
-  y = sel(q2, p.z, sel(q1, p.y, p.x));
-  fp2_mul(o, x, y);  // X^2 | Y^2 | Y Z
-  const fp2 A = quad_bcast<0>(o), B = quad_bcast<1>(o), YZ = quad_bcast<2>(o);
-  fp2 XB, E;
-  fp2_add(XB, p.x, B);
-  fp2_add(E, A, A);
-  fp2_add(E, E, A);
-  x = sel(q2, E, sel(q1, XB, B));
-  fp2_mul(o, x, x);  // C = B^2 | (X + B)^2 | F = E^2
-  const fp2 C = quad_bcast<0>(o), T = quad_bcast<1>(o), Fv = quad_bcast<2>(o);
-  fp2 t, D, x3, c8;
-  fp2_sub(t, T, A);
-  fp2_sub(t, t, C);
-  fp2_add(D, t, t);
-  fp2_sub(x3, Fv, D);
-  fp2_sub(x3, x3, D);
-  fp2_sub(t, D, x3);
-  fp2_mul(t, E, t);
-  fp2_add(c8, C, C);
-  fp2_add(c8, c8, c8);
-  fp2_add(c8, c8, c8);
-  fp2_sub(r.y, t, c8);
-  fp2_add(r.z, YZ, YZ);
-  r.x = x3;
-}
-
-// G2 addition (curve.h jac_add_body, add-2007-bl: 11 products + 5 squarings) dealt out over the quad in five levels
-// of one product per lane, each level broadcast to the quad:
-//   1: Z1^2 | Z2^2 | Y1 Z2 | Y2 Z1          2: U1 = X1 Z2^2 | U2 = X2 Z1^2 | S1 = Y1 Z2^3 | S2 = Y2 Z1^3
-//   3: I = (2H)^2 | R^2 | (Z1 + Z2)^2        4: J = H I | V = U1 I | Z3 = ((Z1 + Z2)^2 - Z1^2 - Z2^2) H
-//   5: R (V - X3) | S1 J
-// Five products of latency instead of sixteen; squarings as products of equal operands (the same canonical values).
-// The exceptional cases (an input at infinity, H = 0) take jac_add on every lane: the values are the same on all
-// four lanes, so those branches are quad-uniform.  All four lanes (and their Fp2 twins) must be active.
-__device__ __forceinline__ void g2_add_quad(g2j& r, const g2j& p, const g2j& qp, int q) {
-  if (jac_is_inf(p) || jac_is_inf(qp)) {
-    jac_add(r, p, qp);
-    return;
-  }
-  const uint32_t q1 = q == 1 ? ~0u : 0u, q2 = q == 2 ? ~0u : 0u, q3 = q == 3 ? ~0u : 0u;
-  fp2 x, y, o;
-  x = sel(q3, qp.y, sel(q2, p.y, sel(q1, qp.z, p.z)));
-  y = sel(q3, p.z, sel(q2, qp.z, sel(q1, qp.z, p.z)));
-  fp2_mul(o, x, y);
-  const fp2 z1z1 = quad_bcast<0>(o), z2z2 = quad_bcast<1>(o), s1a = quad_bcast<2>(o), s2a = quad_bcast<3>(o);
-  x = sel(q3, s2a, sel(q2, s1a, sel(q1, qp.x, p.x)));
-  y = sel(q3, z1z1, sel(q2, z2z2, sel(q1, z1z1, z2z2)));
-  fp2_mul(o, x, y);
-  const fp2 u1 = quad_bcast<0>(o), u2 = quad_bcast<1>(o), s1 = quad_bcast<2>(o), s2 = quad_bcast<3>(o);
-  fp2 h, rr;
-  fp2_sub(h, u2, u1);
-  fp2_sub(rr, s2, s1);
-  if (fp2_is_zero(h)) {  // the same on all four lanes
-    if (fp2_is_zero(rr))
-      jac_dbl(r, p);
-    else
-      jac_set_inf(r);
-    return;
-  }
-  fp2_add(rr, rr, rr);
-  fp2 h2, zs;
-  fp2_add(h2, h, h);
-  fp2_add(zs, p.z, qp.z);
-  x = sel(q2, zs, sel(q1, rr, h2));
-  fp2_mul(o, x, x);
-  const fp2 i = quad_bcast<0>(o), r2 = quad_bcast<1>(o), zz = quad_bcast<2>(o);
-  fp2 zc;
-  fp2_sub(zc, zz, z1z1);
-  fp2_sub(zc, zc, z2z2);
-  x = sel(q2, zc, sel(q1, u1, h));
-  y = sel(q2, h, i);
-  fp2_mul(o, x, y);
-  const fp2 j = quad_bcast<0>(o), v = quad_bcast<1>(o), z3 = quad_bcast<2>(o);
-  fp2 x3, t;
-  fp2_sub(x3, r2, j);
-  fp2_sub(x3, x3, v);
-  fp2_sub(x3, x3, v);
-  fp2_sub(t, v, x3);
-  x = sel(q1, s1, rr);
-  y = sel(q1, j, t);
-  fp2_mul(o, x, y);
-  const fp2 y3a = quad_bcast<0>(o), s1j = quad_bcast<1>(o);
-  fp2 y3, s1j2;
-  fp2_add(s1j2, s1j, s1j);
-  fp2_sub(y3, y3a, s1j2);
-  r.x = x3;
-  r.y = y3;
-  r.z = z3;
-}
-
+// (tagg_lat.h: g2_dbl_quad, g2_add_quad)
 // [|x|] p with the doublings and the additions (at |x|'s five set bits below the top) on the quad
 __device__ void g2_mul_xabs_quad(g2j& r, const g2j& p_in, int q) {
   const g2j p = p_in;
@@ -274,6 +178,83 @@ __global__ void __launch_bounds__(kOctBlock) k_fav_prep8(const uint8_t* __restri
     ((int32_t*)(ws + 120 * G))[2 * i + 1] = ds;
     if (ds == DEC_OK) soa_store<48>(ws + 72 * G, G, i, &sig.x.c0.v[0]);
   }
+}
+
+// The lone sigagg route's stage 1 (hipbls.hip launch_tagg_verify / launch_tagg, at most 4 groups and 64 partials:
+// core/sigagg/sigagg.go:138-159 for one proposer duty), eight lanes per unit, roles uniform per workgroup as
+// k_fav_prep8's: the key blocks (per group: decode + subgroup test + [L] pk and the status, as kernels.h
+// tv_prep_pk2_block), the hash blocks (per group, k_verify_prep8's role 2), then the partial blocks (one octet per
+// partial, tagg_lat.h tagg_scale_octet).  with_keys = 0 (the aggregate-only call): partial blocks only.  ws: [L] pk
+// (24 x G) and H(m) (48 x G), SoA; pts / pstat as k_tagg_scale writes them.  Not raced.
+__global__ void __launch_bounds__(kOctBlock) k_tv_prep8(const uint8_t* __restrict__ pks,
+                                                        const uint8_t* __restrict__ msgs,
+                                                        const uint64_t* __restrict__ moffs, uint64_t G,
+                                                        const int64_t* __restrict__ ids,
+                                                        const uint64_t* __restrict__ goffs, uint32_t* __restrict__ ws,
+                                                        int32_t* __restrict__ vstatus,
+                                                        const uint8_t* __restrict__ sigs, uint64_t n_parts,
+                                                        uint32_t* __restrict__ pts, int32_t* __restrict__ pstat,
+                                                        uint32_t with_keys) {
+  bls_race::init(nullptr, 0u);
+  const uint64_t nbg = with_keys ? (8 * G + kOctBlock - 1) / kOctBlock : 0;
+  uint64_t b = blockIdx.x;
+  int role = 0;  // 0 key, 1 hash, 2 partial: uniform per workgroup
+  if (b >= nbg) {
+    b -= nbg;
+    role = b < nbg ? 1 : 2;
+    if (role == 2) b -= nbg;
+  }
+  const uint64_t t = b * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t i = t >> 3;
+  const bool lead = (t & 7) == 0;
+  if (role == 2) {
+    if (i >= n_parts) return;  // the same on all eight lanes
+    tagg_scale_octet(i, (int)(t & 3), lead, sigs, ids, goffs, G, n_parts, pts, pstat);
+    return;
+  }
+  if (i >= G) return;
+  if (role == 1) {
+    const uint32_t m = (t & 1) ? ~0u : 0u;
+    const uint64_t o0 = moffs[i], o1 = moffs[i + 1];
+    g2j sum, hj;
+    hash_to_g2_pair_sum(sum, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, m);
+    g2_clear_cofactor_quad(hj, sum, (int)(t & 3));
+    g2a hm;
+    jac_to_aff(hm, hj);
+    if (lead) soa_store<48>(ws + 24 * G, G, i, &hm.x.c0.v[0]);
+    return;
+  }
+  g1a pk;
+  const int dp = g1_decompress(pk, pks + 48 * i, true);
+  int st = RLC_PENDING;
+  if (dp == DEC_BAD)
+    st = HIPBLS_ERR_PUBKEY;
+  else if (dp == DEC_INF)
+    st = HIPBLS_ERR_VERIFY;
+  if (st == RLC_PENDING) {
+    const uint64_t g0 = goffs[i], g1 = goffs[i + 1];
+    g1_scale_affine(pk, tagg_group_L(ids + g0, (int)(g1 - g0)));
+    if (lead) soa_store<24>(ws, G, i, &pk.x.v[0]);
+  }
+  if (lead) vstatus[i] = st;
+}
+
+// The aggregate-only lone route's stage 2 (hipbls.hip launch_tagg), one workgroup per group, lanes 0-7: the status
+// and the sum S of the scaled partials, then sigma = [L^-1] S compressed (tagg_lat.h).  Bytes and statuses as
+// k_tagg_sum's.
+__global__ void __launch_bounds__(kOctBlock) k_tagg_sum8(const uint32_t* __restrict__ pts,
+                                                         const int32_t* __restrict__ pstat,
+                                                         const int64_t* __restrict__ ids,
+                                                         const uint64_t* __restrict__ goffs, uint64_t n_parts,
+                                                         uint8_t* __restrict__ out, int32_t* __restrict__ status) {
+  bls_race::init(nullptr, 0u);
+  const uint64_t g = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid >= 8) return;
+  g2j S;
+  const int st = tagg_sum_octet(S, pts, pstat, goffs, g, n_parts, tid & 3);
+  tagg_unscale_octet(S, st, g, ids, goffs, out, tid & 3, tid == 0);
+  if (tid == 0) status[g] = st;
 }
 
 #ifndef BLS_LQ8_XCD_PROBE

@@ -1,0 +1,126 @@
+"""Latency of lone calls on the proposer path (INTEGRATION.md latency table).
+
+A proposal runs randao Verify -> sigagg of one validator -> block Verify -> sigagg of one validator, each step waiting
+for the one before (core/validatorapi/validatorapi.go:320,379,420,479,609; core/sigagg/sigagg.go:138-159).  This tool
+times each of those calls alone, and the chain as one unit, through the synchronous host API (every call ends in a
+device sync and the copy-back, so the host clock covers the whole call):
+
+    HIPBLS_LIB=<another build> python3 charon_amd/tools/lone_latency.py [--calls 200] [--warmup 20]
+
+One process per run; the library comes from HIPBLS_LIB as charon_amd/tbls.py allows (an A/B against another commit's
+build is two processes).  After the clocked pass, a second pass with hipbls_set_timing(1) reports the per-kernel
+averages of the stages the shapes launched.  Prints one JSON object.
+"""
+import argparse
+import ctypes
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+
+R_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+STAGES = ("verify_prep8", "verify_pair_lq16", "verify_pair_lq8", "fav_prep8", "fav_lq16", "fav", "tv_prep8", "tv_lq16",
+          "tagg_sum8", "tv_phase_a", "tv_prep_pk", "tagg_scale", "tagg_sum", "tv_check_unscale", "tagg_unscale",
+          "verify_pair_lq4", "verify_pair_lg2")
+
+
+def _duty(impl, rng, t, total):
+    """One validator's duty: t of its `total` partials, its root key and its 32-byte signing root."""
+    secret = rng.randrange(1, R_ORDER).to_bytes(32, "big")
+    msg = rng.randbytes(32)
+    shares = impl.threshold_split(secret, total, t)
+    ids = sorted(rng.sample(range(1, total + 1), t))
+    sigs, st = impl.sign_batch([shares[i] for i in ids], [msg] * t)
+    assert set(st) == {0}
+    return dict(zip(ids, sigs)), impl.secret_to_public_key(secret), msg, impl.sign(secret, msg)
+
+
+def _fav(impl, rng, nkeys):
+    """One FastAggregateVerify group: nkeys keys over one message and the sum of their signatures."""
+    sks = [rng.randrange(1, R_ORDER).to_bytes(32, "big") for _ in range(nkeys)]
+    msg = rng.randbytes(32)
+    pks, _ = impl.secret_to_public_key_batch(sks)
+    sigs, _ = impl.sign_batch(sks, [msg] * nkeys)
+    return pks, impl.aggregate(sigs), msg
+
+
+def _stats(ms):
+    ms = sorted(ms)
+    return {"p50_ms": round(statistics.median(ms), 4), "p90_ms": round(ms[int(0.9 * (len(ms) - 1))], 4),
+            "min_ms": round(ms[0], 4), "calls": len(ms)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--timing-calls", type=int, default=20)
+    a = ap.parse_args()
+    if a.calls < 200:
+        ap.error("--calls must be at least 200")
+    from charon_amd import tbls
+    impl = tbls.HipBLS()
+    rng = random.Random(0x10E)
+    d46, d710, d710b = _duty(impl, rng, 4, 6), _duty(impl, rng, 7, 10), _duty(impl, rng, 7, 10)
+    fav4, fav12 = _fav(impl, rng, 4), _fav(impl, rng, 12)
+
+    def verify(d):  # a Verify of the duty's aggregate: the randao / block signature check
+        assert impl.batch_verify_status([d[1]], [d[2]], [d[3]]) == [0]
+
+    def sigagg(d):
+        aggs, vst = impl.batch_threshold_aggregate_verify([d[0]], [d[1]], [d[2]])
+        assert aggs == [d[3]] and vst == [0]
+
+    def tagg(d):
+        assert impl.batch_threshold_aggregate([d[0]]) == [d[3]]
+
+    def fav(f):
+        assert impl.batch_verify_aggregate_status([f]) == [0]
+
+    def chain():
+        verify(d710)
+        sigagg(d710)
+        verify(d710b)
+        sigagg(d710b)
+
+    shapes = [("verify_1", lambda: verify(d710)), ("fav_1x4", lambda: fav(fav4)), ("fav_1x12", lambda: fav(fav12)),
+              ("sigagg_4of6", lambda: sigagg(d46)), ("sigagg_7of10", lambda: sigagg(d710)),
+              ("tagg_7of10", lambda: tagg(d710)), ("chain_verify_sigagg_x2", chain)]
+    for _, fn in shapes:
+        for _ in range(a.warmup):
+            fn()
+    out = {"lib": os.environ.get("HIPBLS_LIB") or "in-tree", "build_id": tbls.build_id().get("src", "")[:16],
+           "calls": a.calls, "warmup": a.warmup, "shapes": {}, "kernels_ms": {}}
+    for name, fn in shapes:
+        ms = []
+        for _ in range(a.calls):
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        out["shapes"][name] = _stats(ms)
+    # per-kernel averages, in a pass of their own: the event pairs around each launch are not in the clocked calls
+    impl.lib.hipbls_kernel_timing_reset()
+    impl.lib.hipbls_set_timing(1)
+    try:
+        for name, fn in shapes[:-1]:
+            impl.lib.hipbls_kernel_timing_reset()
+            for _ in range(a.timing_calls):
+                fn()
+            per = {}
+            for st in STAGES:
+                avg, cnt = ctypes.c_double(), ctypes.c_uint64()
+                impl.lib.hipbls_kernel_timing(st.encode(), ctypes.byref(avg), ctypes.byref(cnt))
+                if cnt.value:
+                    per[st] = round(avg.value, 4)
+            out["kernels_ms"][name] = per
+    finally:
+        impl.lib.hipbls_set_timing(0)
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()

@@ -115,8 +115,11 @@ int hipbls_set_timing(int enabled);
  * layout with every Fp2 product and square split across twin lanes, charon_amd/csrc/verify_lat.hip: the drop-in
  * n = 1 latency path; other checks as QUADS).  HIPBLS_PAIR_AUTO (default): the widest layout the batch leaves
  * lanes for (Verify: octets up to 4,096 items, quads up to the quad limit, then pairs up to 32,768 items; RLC
- * sub-batches up to 32,768 windows, every RLC fallback list and FastAggregateVerify on pairs).  Results are
- * identical in every mode.  Returns the previous mode, or HIPBLS_ERR_ARG for an unknown one.  The environment
+ * sub-batches up to 32,768 windows, every RLC fallback list and FastAggregateVerify on pairs).  AUTO alone also
+ * takes the lone sigagg route: a threshold-aggregate(-verify) call of at most 4 groups and 64 partials runs its keys,
+ * hashes and partials on octets and its check on sixteen lanes; every forced mode keeps the
+ * throughput kernels, HIPBLS_LAT_HEX=0 turns the sixteen-lane paths off, HIPBLS_LAT_SIGAGG=0 this route alone.
+ * Results are identical in every mode.  Returns the previous mode, or HIPBLS_ERR_ARG for an unknown one.  The environment
  * variable HIPBLS_PAIR_MODE (0-4) sets the initial mode. */
 enum { HIPBLS_PAIR_AUTO = 0, HIPBLS_PAIR_SINGLE = 1, HIPBLS_PAIR_LANES = 2, HIPBLS_PAIR_QUADS = 3,
        HIPBLS_PAIR_OCTETS = 4 };
@@ -167,7 +170,10 @@ int hipbls_verify_signed_data_batch(const uint8_t* pks, const uint8_t* object_ro
  * sigs[96 k ..], share_idx[k] for k in [group_offsets[g], group_offsets[g+1]).
  * out_sigs[96 g ..] = sum_k lambda_k(0) * sig_k: Lagrange at 0 over the share indices taken as Fr elements the
  * way herumi parses strconv.Itoa(idx) (tbls/herumi.go:264-271): a signed Go int reduced mod r, so -k is r - k.
- * status[g] = HIPBLS_OK | HIPBLS_ERR_SIGNATURE | HIPBLS_ERR_COMBINE (empty set, id = 0, duplicate id). */
+ * status[g] = HIPBLS_OK | HIPBLS_ERR_SIGNATURE | HIPBLS_ERR_COMBINE (empty set, id = 0, duplicate id).
+ * A lone call (at most 4 groups and 64 partials, HIPBLS_PAIR_AUTO) takes the latency route: one octet of lanes per
+ * partial, then per group the sum and [L^-1] S on an octet (kernels timed as tv_prep8, tagg_sum8).
+ * Same bytes and statuses. */
 int hipbls_threshold_aggregate_batch(const uint8_t* sigs, const int64_t* share_idx,
                                      const uint64_t* group_offsets, uint64_t n_groups,
                                      uint8_t* out_sigs, int32_t* status);
@@ -277,7 +283,11 @@ int hipbls_verify_batch_device(const uint8_t* d_pks, const uint8_t* d_msgs, cons
  * hipbls_threshold_aggregate_batch: out_sigs, agg_status) and Verify(dv_pks[g], msg g, out_sigs[g]) of each
  * aggregate (verify_status, as hipbls_verify_batch).  A group whose aggregation failed reports its aggregation
  * status in verify_status too.  The key decode and hash run beside the aggregation, and the aggregate goes to the
- * pairing check without being decompressed again: the same verdicts as the two calls, in less time. */
+ * pairing check without being decompressed again: the same verdicts as the two calls, in less time.
+ * A lone call -- one proposer duty: at most 4 groups and 64 partials, however they are split over the groups, in
+ * HIPBLS_PAIR_AUTO -- takes the latency route instead of one lane per unit of work: keys, hashes and partials on
+ * octets, then per group the sum, the check on sixteen lanes and [L^-1] S beside it (two kernels, timed as tv_prep8
+ * and tv_lq16).  Same bytes and statuses. */
 int hipbls_threshold_aggregate_verify_batch(const uint8_t* sigs, const int64_t* share_idx,
                                             const uint64_t* group_offsets, uint64_t n_groups, const uint8_t* dv_pks,
                                             const uint8_t* msgs, const uint64_t* msg_offsets, uint8_t* out_sigs,
