@@ -78,6 +78,11 @@ __global__ void k_tv_prep8(const uint8_t* pks, const uint8_t* msgs, const uint64
                            const uint8_t* sigs, uint64_t n_parts, uint32_t* pts, int32_t* pstat, uint32_t with_keys);
 __global__ void k_tagg_sum8(const uint32_t* pts, const int32_t* pstat, const int64_t* ids, const uint64_t* goffs,
                             uint64_t n_parts, uint8_t* out, int32_t* status);
+__global__ void k_tv_prep8_keys(const uint32_t* key_idx, uint64_t T, const int32_t* tcode, const uint32_t* tab,
+                                const uint8_t* msgs, const uint64_t* moffs, const uint32_t* mlist, uint64_t n_hash,
+                                uint64_t n_msgs, uint32_t* Hc, uint64_t G, const int64_t* ids, const uint64_t* goffs,
+                                uint32_t* ws, int32_t* vstatus, const uint8_t* sigs, uint64_t n_parts, uint32_t* pts,
+                                int32_t* pstat);
 }  // namespace bls_fp2p
 // The sixteen-lane check for batches of at most four items (verify_hex.hip: BLS_FP2_PAIR + BLS_HEX, namespace bls_hex).
 namespace bls_hex {
@@ -211,6 +216,7 @@ struct Context {
   // sigagg in one call (launch_tagg_verify): two workspace sets used alternately, each with the completion event of
   // the call that last used it
   DevBuf tv_pts[2], tv_pst[2], tv_ws[2], tv_aux[2];
+  DevBuf tv_h[2];  // the keyed call's own H(m) table (the messages it hashed itself), per workspace set
   // The host-buffer sigagg call (tagg_verify_host): two slots of input/output buffers, used alternately, each on its
   // own library sub-stream; a call holds its slot for its whole duration but the context lock only while it enqueues,
   // so the next caller's copies and phase A run beside this call's checks (the _device path's two-stream overlap,
@@ -218,6 +224,7 @@ struct Context {
   struct TvHostSlot {
     std::mutex mu;
     DevBuf sig, ids, off, pk, msg, moff, out, st;
+    DevBuf kidx, midx, hsrc, mlist;  // the keyed call: key and message indices, H(m) sources, miss list
     uint8_t* h_out = nullptr;  // pinned: the outputs come back by a real async D2H
     int32_t* h_st = nullptr;
     uint64_t h_groups = 0;
@@ -225,6 +232,9 @@ struct Context {
   } tvh[2];
   std::atomic<uint64_t> tvh_seq{0};
   hipEvent_t tv_done[2] = {}, tv_phase = nullptr;  // tv_phase: the last call's phase A (and S, statuses) done
+  // The keyed sigagg call's last read of the H(m) cache (its gather): an RLC call that is about to overwrite cache
+  // columns waits on it (rlc_host_on).  Null until a keyed call has read the cache.
+  hipEvent_t tv_hread = nullptr;
   uint64_t tv_seq = 0;
   uint64_t t_size = 0;
   // pubshare bytes -> table index (host side), for the submission queue's keyed path
@@ -368,6 +378,7 @@ const KernelRef kKernels[] = {
     KREF8(k_rlcb_final8), KREF8(k_rlcb_sfactor8), KREF8(k_verify_pair_lq8), KREF8(k_verify_prep8),
     KREF16(k_verify_pair_lq16), KREF8(k_fav_prep8), KREF16W(k_fav_pair_lq16),
     KREF8(k_tv_prep8), KREF8(k_tagg_sum8), KREF16(k_tv_pair_lq16),
+    KREF(k_tv_phase_a_keys), KREF(k_tv_join_keys), KREF(k_tv_gather_keys), KREF8(k_tv_prep8_keys),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -1539,9 +1550,24 @@ int launch_tagg(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const u
 #ifndef BLS_TV_PAIR_HASH
 #define BLS_TV_PAIR_HASH 1
 #endif
+// The keyed form (hipbls_threshold_aggregate_verify_batch_keys[_device]): root keys by index into the resident table,
+// messages by index into n_msgs distinct ones (d_msgs / d_moffs are that table's).  H(m) of a message comes from the
+// context's H(m) cache where d_hsrc says so (kernels.h kTvHCached) and otherwise from the call's own table tv_h[p],
+// which phase A fills for the n_hash messages of d_mlist (nullptr: messages 0 .. n_hash - 1).  The cache is read only
+// by the gather, inside phase A (before tv_phase is recorded): after the RLC call that filled the columns (ws_done_rlc)
+// and, through tv_hread, before any later RLC call overwrites them.  device = true: the indices were not checked on
+// the host, an out-of-range one is ERR_ARG for its group.
+struct TvKeys {
+  const uint32_t *d_kidx, *d_midx;
+  uint64_t n_msgs;
+  const uint32_t *d_hsrc, *d_mlist;
+  uint64_t n_hash;
+  bool reads_cache, device;
+};
 int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const uint64_t* d_goffs,
                        uint64_t n_groups, uint64_t n_parts, const uint8_t* d_dvpks, const uint8_t* d_msgs,
-                       const uint64_t* d_moffs, uint8_t* d_out, int32_t* d_astatus, int32_t* d_vstatus, hipStream_t s) {
+                       const uint64_t* d_moffs, uint8_t* d_out, int32_t* d_astatus, int32_t* d_vstatus, hipStream_t s,
+                       const TvKeys* K = nullptr) {
   if (n_groups == 0) return HIPBLS_OK;
   const int p = (int)(c.tv_seq & 1);
   if (!c.tv_done[p]) HIP_TRY(hipEventCreateWithFlags(&c.tv_done[p], hipEventDisableTiming));
@@ -1549,6 +1575,8 @@ int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, 
   HIP_TRY(c.tv_pst[p].ensure((n_parts ? n_parts : 1) * 4));
   HIP_TRY(c.tv_ws[p].ensure(n_groups * 120 * 4));
   HIP_TRY(c.tv_aux[p].ensure(n_groups * 4));
+  if (K) HIP_TRY(c.tv_h[p].ensure((K->n_msgs ? K->n_msgs : 1) * 48 * 4));
+  if (K && K->reads_cache && !c.tv_hread) HIP_TRY(hipEventCreateWithFlags(&c.tv_hread, hipEventDisableTiming));
   ++c.tv_seq;
   uint32_t* ws = (uint32_t*)c.tv_ws[p].p;
   int32_t* agg_inf = (int32_t*)c.tv_aux[p].p;
@@ -1573,6 +1601,44 @@ int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, 
   // wave slots, while this call's phase A beside the previous call's check fills the SIMDs that check leaves idle.
   HIP_TRY(hipStreamWaitEvent(s, c.tv_phase, 0));
   int rc = HIPBLS_OK;
+  // the keyed call's tables: the resident keys, the H(m) cache and the call's own H(m) columns
+  const uint64_t T = c.t_size, cstride = c.hcache.cap;
+  const int32_t* tcode = (const int32_t*)c.t_code.p;
+  const uint32_t* tab = (const uint32_t*)c.t_tab.p;
+  const uint32_t* Hcache = (const uint32_t*)c.hcache.table.p;
+  uint32_t* Hc = (uint32_t*)c.tv_h[p].p;
+  if (K && K->reads_cache) HIP_TRY(hipStreamWaitEvent(s, c.ws_done_rlc, 0));
+  if (K && use_tagg_lat(n_groups, n_parts)) {
+    const uint64_t nbg = (8 * n_groups + kBlock - 1) / kBlock, nbh = (8 * K->n_hash + kBlock - 1) / kBlock,
+                   nbp = (8 * n_parts + kBlock - 1) / kBlock;
+    rc = timed(c, "tv_prep8_keys", s, [&] {
+      hipLaunchKernelGGL(bls_fp2p::k_tv_prep8_keys, dim3((unsigned)(nbg + nbh + nbp)), dim3(kBlock), 0, s, K->d_kidx,
+                         T, tcode, tab, d_msgs, d_moffs, K->d_mlist, K->n_hash, K->n_msgs, Hc, n_groups, d_ids,
+                         d_goffs, ws, d_vstatus, d_sigs, n_parts, pts, pst);
+    });
+    if (rc) return rc;
+    // the gather is a kernel of its own here, not a prologue of stage 2: k_tv_pair_lq16 stays as it is, and the cache
+    // is not read after tv_phase
+    const auto gather = [&](uint32_t after) {
+      hipLaunchKernelGGL(k_tv_gather_keys, dim3((unsigned)grid_for(48 * n_groups)), dim3(kBlock), 0, s, n_groups,
+                         K->d_kidx, T, K->d_midx, K->n_msgs, K->d_hsrc, Hcache, cstride, (const uint32_t*)Hc,
+                         d_vstatus, ws, after);
+    };
+    rc = timed(c, "tv_gather_keys", s, [&] { gather(0u); });
+    if (rc) return rc;
+    if (K->reads_cache) HIP_TRY(hipEventRecord(c.tv_hread, s));
+    HIP_TRY(hipEventRecord(c.tv_phase, s));
+    tv_end.phase = true;
+    rc = timed(c, "tv_lq16", s, [&] {
+      hipLaunchKernelGGL(bls_hex::k_tv_pair_lq16, dim3((unsigned)(2 * n_groups)), dim3(kBlock), 0, s,
+                         (const uint32_t*)pts, (const int32_t*)pst, d_ids, d_goffs, n_groups, n_parts,
+                         (const uint32_t*)ws, d_astatus, d_vstatus, d_out);
+    });
+    if (rc || !K->device) return rc;
+    gather(1u);  // ERR_ARG stands where the aggregation failed too
+    HIP_TRY(hipGetLastError());
+    return HIPBLS_OK;  // tv_end records tv_done[p]
+  }
   if (use_tagg_lat(n_groups, n_parts)) {
     // the kernel derives the same role boundaries from n_groups and n_parts
     const uint64_t nbg = (8 * n_groups + kBlock - 1) / kBlock, nbp = (8 * n_parts + kBlock - 1) / kBlock;
@@ -1589,7 +1655,16 @@ int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, 
                          (const uint32_t*)ws, d_astatus, d_vstatus, d_out);
     });  // tv_end records tv_done[p]
   }
-  if (BLS_TV_PAIR_HASH && n_groups <= kPairHashMaxVerify) {
+  if (K) {
+    // one launch whatever the group count: the hash role covers the miss list only, always on lane pairs
+    const uint64_t nprep = grid_for(n_groups) + (K->n_hash ? grid_for(2 * K->n_hash) : 0),
+                   nscale = n_parts ? grid_for(n_parts) : 0;
+    rc = timed(c, "tv_phase_a_keys", s, [&] {
+      hipLaunchKernelGGL(k_tv_phase_a_keys, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, K->d_kidx, T, tcode,
+                         tab, d_msgs, d_moffs, K->d_mlist, K->n_hash, K->n_msgs, Hc, n_groups, d_ids, d_goffs, ws,
+                         d_vstatus, d_sigs, n_parts, pts, pst);
+    });
+  } else if (BLS_TV_PAIR_HASH && n_groups <= kPairHashMaxVerify) {
     const uint64_t nprep = 3 * grid_for(n_groups), nscale = n_parts ? grid_for(n_parts) : 0;
     rc = timed(c, "tv_phase_a", s, [&] {
       hipLaunchKernelGGL(k_tv_phase_a, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, d_dvpks, d_msgs, d_moffs,
@@ -1613,9 +1688,17 @@ int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, 
                        (const int32_t*)pst, d_goffs, n_groups, n_parts, d_astatus, ws, agg_inf);
   });
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tv_join, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, n_groups,
-                     (const int32_t*)d_astatus, (const int32_t*)agg_inf, d_vstatus);
-  HIP_TRY(hipGetLastError());
+  if (K) {
+    hipLaunchKernelGGL(k_tv_join_keys, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, n_groups, K->d_kidx, T,
+                       K->d_midx, K->n_msgs, K->d_hsrc, Hcache, cstride, (const uint32_t*)Hc,
+                       (const int32_t*)d_astatus, (const int32_t*)agg_inf, d_vstatus, ws);
+    HIP_TRY(hipGetLastError());
+    if (K->reads_cache) HIP_TRY(hipEventRecord(c.tv_hread, s));
+  } else {
+    hipLaunchKernelGGL(k_tv_join, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, n_groups,
+                       (const int32_t*)d_astatus, (const int32_t*)agg_inf, d_vstatus);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipEventRecord(c.tv_phase, s));
   tv_end.phase = true;
   if (use_quads(n_groups)) {
@@ -1812,6 +1895,8 @@ int rlc_host_on(Context& c, RlcBufs B, hipStream_t s, const uint8_t* pks, const 
     // the copies run on s behind every earlier workspace user (ws_done): the slot table is per call
     int rc = ws_begin(c, s, WS_RLC);
     if (rc) return rc;
+    // a keyed sigagg call may still be gathering H(m) from columns this call's misses are about to take
+    if (c.tv_hread && miss.size()) HIP_TRY(hipStreamWaitEvent(s, c.tv_hread, 0));
     if (n_msgs) HIP_TRY(hipMemcpyAsync(B.slot->p, slot.data(), n_msgs * 4, hipMemcpyHostToDevice, s));
     if (miss.size()) HIP_TRY(hipMemcpyAsync(B.mlist->p, miss.data(), miss.size() * 4, hipMemcpyHostToDevice, s));
     dH = (uint32_t*)c.hcache.table.p;
@@ -2285,11 +2370,20 @@ int tagg_host(Context& c, const uint8_t* sigs, const int64_t* share_idx, const u
 // Called WITHOUT the context lock (run_ranges_unlocked): it takes a host slot for the whole call and the context lock
 // only to enqueue (copies in, the sigagg kernels, copies out into the slot's pinned buffers), then waits for the slot's
 // completion event with no lock held.
+// The keyed form (HK): dv_pks is null, msgs / moffs hold HK->n_msgs distinct messages, and each of them is looked up
+// in the context's H(m) cache under the context lock -- read only: sigagg is the last consumer of a root, so it neither
+// inserts nor evicts; a miss is hashed into the call's own table.
+struct TvHostKeys {
+  const uint32_t *key_idx, *msg_idx;
+  uint64_t n_msgs;
+};
 int tagg_verify_host(Context& c, const uint8_t* sigs, const int64_t* share_idx, const uint64_t* goffs,
                      uint64_t n_groups, const uint8_t* dv_pks, const uint8_t* msgs, const uint64_t* moffs,
-                     uint8_t* out_sigs, int32_t* agg_status, int32_t* verify_status) {
+                     uint8_t* out_sigs, int32_t* agg_status, int32_t* verify_status,
+                     const TvHostKeys* HK = nullptr) {
   const uint64_t n_parts = goffs[n_groups];
-  const uint64_t msg_total = moffs[n_groups];
+  const uint64_t n_moffs = HK ? HK->n_msgs : n_groups;
+  const uint64_t msg_total = moffs[n_moffs];
   const int p = (int)(c.tvh_seq.fetch_add(1) & 1);
   Context::TvHostSlot& h = c.tvh[p];
   std::lock_guard<std::mutex> slot_lock(h.mu);
@@ -2306,6 +2400,7 @@ int tagg_verify_host(Context& c, const uint8_t* sigs, const int64_t* share_idx, 
     HIP_TRY(hipHostMalloc((void**)&h.h_st, n_groups * 8, hipHostMallocDefault));
     h.h_groups = n_groups;
   }
+  std::vector<uint32_t> hsrc, mlist;  // the keyed call's H(m) sources and miss list: alive until the copies are done
   {
     std::lock_guard<std::mutex> lk(c.mu);
     const hipStream_t s = c.sub[p];
@@ -2322,9 +2417,9 @@ int tagg_verify_host(Context& c, const uint8_t* sigs, const int64_t* share_idx, 
     HIP_TRY(h.sig.ensure((n_parts ? n_parts : 1) * 96));
     HIP_TRY(h.ids.ensure((n_parts ? n_parts : 1) * 8));
     HIP_TRY(h.off.ensure((n_groups + 1) * 8));
-    HIP_TRY(h.pk.ensure(n_groups * 48));
+    if (!HK) HIP_TRY(h.pk.ensure(n_groups * 48));
     HIP_TRY(h.msg.ensure(msg_total ? msg_total : 1));
-    HIP_TRY(h.moff.ensure((n_groups + 1) * 8));
+    HIP_TRY(h.moff.ensure((n_moffs + 1) * 8));
     HIP_TRY(h.out.ensure(n_groups * 96));
     HIP_TRY(h.st.ensure(n_groups * 8));  // aggregate statuses, then verify statuses
     if (n_parts) {
@@ -2332,14 +2427,46 @@ int tagg_verify_host(Context& c, const uint8_t* sigs, const int64_t* share_idx, 
       HIP_TRY(hipMemcpyAsync(h.ids.p, share_idx, n_parts * 8, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(hipMemcpyAsync(h.off.p, goffs, (n_groups + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h.pk.p, dv_pks, n_groups * 48, hipMemcpyHostToDevice, s));
+    if (!HK) HIP_TRY(hipMemcpyAsync(h.pk.p, dv_pks, n_groups * 48, hipMemcpyHostToDevice, s));
     if (msg_total) HIP_TRY(hipMemcpyAsync(h.msg.p, msgs, msg_total, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h.moff.p, moffs, (n_groups + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h.moff.p, moffs, (n_moffs + 1) * 8, hipMemcpyHostToDevice, s));
     int32_t* ast = (int32_t*)h.st.p;
     int32_t* vst = ast + n_groups;
+    TvKeys K{};
+    if (HK) {
+      for (uint64_t g = 0; g < n_groups; ++g)
+        if (HK->key_idx[g] >= c.t_size) return arg_err("key index outside the pubshare table");
+      HCache& hc = c.hcache;
+      hsrc.resize(HK->n_msgs ? HK->n_msgs : 1);
+      bool any_hit = false;
+      for (uint64_t m = 0; m < HK->n_msgs; ++m) {
+        auto it = hc.cap ? hc.map.find(std::string((const char*)msgs + moffs[m], moffs[m + 1] - moffs[m]))
+                         : hc.map.end();
+        if (it != hc.map.end()) {
+          hsrc[m] = kTvHCached | (uint32_t)it->second;
+          hc.hits += 1;
+          any_hit = true;
+        } else {
+          hsrc[m] = (uint32_t)m;
+          mlist.push_back((uint32_t)m);
+          hc.misses += 1;
+        }
+      }
+      HIP_TRY(h.kidx.ensure(n_groups * 4));
+      HIP_TRY(h.midx.ensure(n_groups * 4));
+      HIP_TRY(h.hsrc.ensure(hsrc.size() * 4));
+      HIP_TRY(h.mlist.ensure((mlist.size() ? mlist.size() : 1) * 4));
+      HIP_TRY(hipMemcpyAsync(h.kidx.p, HK->key_idx, n_groups * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(h.midx.p, HK->msg_idx, n_groups * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(h.hsrc.p, hsrc.data(), hsrc.size() * 4, hipMemcpyHostToDevice, s));
+      if (mlist.size())
+        HIP_TRY(hipMemcpyAsync(h.mlist.p, mlist.data(), mlist.size() * 4, hipMemcpyHostToDevice, s));
+      K = TvKeys{(const uint32_t*)h.kidx.p, (const uint32_t*)h.midx.p, HK->n_msgs, (const uint32_t*)h.hsrc.p,
+                 (const uint32_t*)h.mlist.p, mlist.size(), any_hit, false};
+    }
     const int rc = launch_tagg_verify(c, (const uint8_t*)h.sig.p, (const int64_t*)h.ids.p, (const uint64_t*)h.off.p,
                                       n_groups, n_parts, (const uint8_t*)h.pk.p, (const uint8_t*)h.msg.p,
-                                      (const uint64_t*)h.moff.p, (uint8_t*)h.out.p, ast, vst, s);
+                                      (const uint64_t*)h.moff.p, (uint8_t*)h.out.p, ast, vst, s, HK ? &K : nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h.h_out, h.out.p, n_groups * 96, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h.h_st, h.st.p, n_groups * 8, hipMemcpyDeviceToHost, s));
@@ -2825,6 +2952,87 @@ int hipbls_threshold_aggregate_verify_batch_device(const uint8_t* d_sigs, const 
   ON_STREAM(c, stream, s);
   return launch_tagg_verify(c, d_sigs, d_share_idx, d_group_offsets, n_groups, n_parts, d_dv_pks, d_msgs,
                             d_msg_offsets, d_out_sigs, d_agg_status, d_verify_status, s);
+}
+
+// Whole groups per device, as the unkeyed call; each range gets its own message table (the messages its groups use,
+// renumbered in first-use order, as rlc_range) and runs against its own context's table copy and H(m) cache.
+int hipbls_threshold_aggregate_verify_batch_keys(const uint8_t* sigs, const int64_t* share_idx,
+                                                 const uint64_t* group_offsets, uint64_t n_groups,
+                                                 const uint32_t* dv_key_idx, const uint32_t* msg_idx,
+                                                 const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t n_msgs,
+                                                 uint8_t* out_sigs, int32_t* agg_status, int32_t* verify_status) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!group_offsets || !dv_key_idx || !msg_idx || !msg_offsets || !out_sigs || !agg_status || !verify_status ||
+      mul_overflows(n_groups, 120 * 4) || mul_overflows(n_msgs, 48 * 4) || n_msgs > 0x7fffffffull)
+    return arg_err("bad arguments");
+  if (!groups_ok(group_offsets, n_groups)) return arg_err("bad group offsets");
+  for (uint64_t g = 0; g < n_groups; ++g)
+    if (msg_idx[g] >= n_msgs) return arg_err("message index out of range");
+  if (!offsets_ok(msg_offsets, n_msgs)) return arg_err("bad message offsets");
+  const uint64_t n_parts = group_offsets[n_groups];
+  if (n_parts && (!sigs || !share_idx)) return arg_err("null partials");
+  if (msg_offsets[n_msgs] && !msgs) return arg_err("null messages");
+  if (mul_overflows(n_parts, 288)) return arg_err("too many partials");
+  ENSURE_INIT();
+  uint64_t T = 0;
+  {
+    std::lock_guard<std::mutex> lk(ctx(0).mu);
+    T = ctx(0).t_size;
+  }
+  for (uint64_t g = 0; g < n_groups; ++g)
+    if (dv_key_idx[g] >= T) return arg_err("key index outside the pubshare table");
+  const std::vector<uint64_t> b = plan_ranges(n_groups, parts_for(n_groups, kSplitGroups), nullptr);
+  const bool whole = b.size() == 2;
+  return run_ranges_unlocked(b, [&](Context& c, uint64_t lo, uint64_t hi) {
+    std::vector<uint64_t> tg;
+    const uint64_t p0 = group_offsets[lo];
+    const uint8_t* rs = sigs ? sigs + 96 * p0 : sigs;
+    const int64_t* ri = share_idx ? share_idx + p0 : share_idx;
+    if (whole) {
+      const TvHostKeys HK{dv_key_idx, msg_idx, n_msgs};
+      return tagg_verify_host(c, rs, ri, group_offsets, n_groups, nullptr, msgs, msg_offsets, out_sigs, agg_status,
+                              verify_status, &HK);
+    }
+    std::unordered_map<uint32_t, uint32_t> local;
+    std::vector<uint32_t> lmidx(hi - lo), used;
+    for (uint64_t g = lo; g < hi; ++g) {
+      auto it = local.find(msg_idx[g]);
+      if (it == local.end()) {
+        it = local.emplace(msg_idx[g], (uint32_t)used.size()).first;
+        used.push_back(msg_idx[g]);
+      }
+      lmidx[g - lo] = it->second;
+    }
+    std::vector<uint64_t> loff(used.size() + 1, 0);
+    for (size_t k = 0; k < used.size(); ++k)
+      loff[k + 1] = loff[k] + (msg_offsets[used[k] + 1] - msg_offsets[used[k]]);
+    std::vector<uint8_t> lmsg(loff.back() ? loff.back() : 1);
+    for (size_t k = 0; k < used.size(); ++k)
+      memcpy(lmsg.data() + loff[k], msgs + msg_offsets[used[k]], loff[k + 1] - loff[k]);
+    const TvHostKeys HK{dv_key_idx + lo, lmidx.data(), used.size()};
+    return tagg_verify_host(c, rs, ri, rebase(group_offsets, lo, hi, tg), hi - lo, nullptr, lmsg.data(), loff.data(),
+                            out_sigs + 96 * lo, agg_status + lo, verify_status + lo, &HK);
+  });
+}
+
+int hipbls_threshold_aggregate_verify_batch_keys_device(
+    const uint8_t* d_sigs, const int64_t* d_share_idx, const uint64_t* d_group_offsets, uint64_t n_groups,
+    uint64_t n_parts, const uint32_t* d_dv_key_idx, const uint32_t* d_msg_idx, const uint8_t* d_msgs,
+    const uint64_t* d_msg_offsets, uint64_t n_msgs, uint8_t* d_out_sigs, int32_t* d_agg_status,
+    int32_t* d_verify_status, void* stream) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (mul_overflows(n_parts, 288) || mul_overflows(n_groups, 120 * 4) || mul_overflows(n_msgs, 48 * 4) ||
+      n_msgs > 0x7fffffffull)
+    return arg_err("too many items");
+  if (!d_dv_key_idx || !d_msg_idx) return arg_err("null indices");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_agg_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  // the host never sees the messages: every distinct one is hashed into the call's own table, the cache is untouched
+  const TvKeys K{d_dv_key_idx, d_msg_idx, n_msgs, nullptr, nullptr, n_msgs, false, true};
+  return launch_tagg_verify(c, d_sigs, d_share_idx, d_group_offsets, n_groups, n_parts, nullptr, d_msgs,
+                            d_msg_offsets, d_out_sigs, d_agg_status, d_verify_status, s, &K);
 }
 
 int hipbls_threshold_aggregate_batch_device(const uint8_t* d_sigs, const int64_t* d_share_idx,

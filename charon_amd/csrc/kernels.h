@@ -462,6 +462,110 @@ __global__ void __launch_bounds__(kBlock) k_tv_join(uint64_t n, const int32_t* _
     vstatus[i] = HIPBLS_ERR_VERIFY;
 }
 
+// ---------------------------------------------------------------- sigagg with keys by table index
+// hipbls_threshold_aggregate_verify_batch_keys: group i's root key is table[key_idx[i]] (rlc.h tv_key_lane: no decode,
+// no subgroup test) and its message is msgs[msg_idx[i]] of n_msgs DISTINCT messages.  H(m) of message m comes from
+// one of two SoA tables: the context's H(m) cache (stride cstride) when hsrc[m] has bit 31 set, column hsrc[m] & ~bit
+// 31, else column m of the call's own table Hc (stride n_msgs), which phase A fills for the miss list only.  hsrc ==
+// nullptr (the _device call, no cache): every message is in Hc.
+constexpr uint32_t kTvHCached = 0x80000000u;
+__device__ __forceinline__ uint32_t tv_h_word(uint32_t m, int w, const uint32_t* __restrict__ hsrc,
+                                              const uint32_t* __restrict__ Hcache, uint64_t cstride,
+                                              const uint32_t* __restrict__ Hc, uint64_t n_msgs) {
+  const uint32_t src = hsrc ? hsrc[m] : m;
+  return (src & kTvHCached) ? Hcache[(uint64_t)w * cstride + (src & ~kTvHCached)] : Hc[(uint64_t)w * n_msgs + m];
+}
+
+// Phase A as ONE launch, roles uniform per workgroup as k_tv_phase_a: workgroups [0, grid_for(n)) take the keys from
+// the table (one lane per group: status and [L] pk), the next grid_for(2 n_hash) hash the n_hash messages of the miss
+// list (mlist, or 0 .. n_hash - 1 without one) on lane pairs into Hc, the rest are k_tagg_scale's.  The prep workgroups
+// come first.  ws gets no H(m) here: k_tv_join_keys gathers it.
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLS_TAGG_WAVES, BLS_TAGG_WAVES)))
+k_tv_phase_a_keys(const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+                  const uint32_t* __restrict__ tab, const uint8_t* __restrict__ msgs,
+                  const uint64_t* __restrict__ offs, const uint32_t* __restrict__ mlist, uint64_t n_hash,
+                  uint64_t n_msgs, uint32_t* __restrict__ Hc, uint64_t n, const int64_t* __restrict__ ids,
+                  const uint64_t* __restrict__ goffs, uint32_t* __restrict__ ws, int32_t* __restrict__ vstatus,
+                  const uint8_t* __restrict__ sigs, uint64_t n_parts, uint32_t* __restrict__ pts,
+                  int32_t* __restrict__ pstat) {
+  const uint64_t nkey = (n + kBlock - 1) / kBlock, nhash = (2 * n_hash + kBlock - 1) / kBlock;
+  if (blockIdx.x < nkey) {
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t g0 = goffs[i], g1 = goffs[i + 1];
+    g1a pk;
+    const int st = tv_key_lane(pk, key_idx[i], T, tcode, tab, ids + g0, (int)(g1 - g0));
+    if (st == RLC_PENDING) soa_store<24>(ws, n, i, &pk.x.v[0]);
+    vstatus[i] = st;
+    return;
+  }
+  if (blockIdx.x < nkey + nhash) {
+    const uint64_t t = (blockIdx.x - nkey) * (uint64_t)blockDim.x + threadIdx.x;
+    const uint64_t j = t >> 1;
+    if (j >= n_hash) return;  // same on both lanes of the pair
+    const uint32_t mask = (t & 1) ? ~0u : 0u;
+    const uint64_t m = mlist ? mlist[j] : j;
+    const uint64_t o0 = offs[m], o1 = offs[m + 1];
+    g2j hj;
+    hash_to_g2_pair(hj, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, mask);
+    if (!mask) {
+      g2a hm;
+      jac_to_aff(hm, hj);
+      soa_store<48>(Hc, n_msgs, m, &hm.x.c0.v[0]);
+    }
+    return;
+  }
+  tagg_scale_lane((blockIdx.x - nkey - nhash) * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n, n_parts, pts,
+                  pstat);
+}
+
+// k_tv_join with the gather: group i's H(m) goes from its table (cache column or the call's own) into ws, the last
+// read of the cache this call makes.  A key or message index out of range (the _device call; the host call refuses
+// them up front) is ERR_ARG, which stands whatever the aggregation gave.
+__global__ void __launch_bounds__(kBlock) k_tv_join_keys(uint64_t n, const uint32_t* __restrict__ key_idx, uint64_t T,
+                                                         const uint32_t* __restrict__ msg_idx, uint64_t n_msgs,
+                                                         const uint32_t* __restrict__ hsrc,
+                                                         const uint32_t* __restrict__ Hcache, uint64_t cstride,
+                                                         const uint32_t* __restrict__ Hc,
+                                                         const int32_t* __restrict__ astatus,
+                                                         const int32_t* __restrict__ agg_inf,
+                                                         int32_t* __restrict__ vstatus, uint32_t* __restrict__ ws) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t m = msg_idx[i];
+  if (key_idx[i] >= T || m >= n_msgs) {
+    vstatus[i] = HIPBLS_ERR_ARG;
+    return;
+  }
+  for (int w = 0; w < 48; ++w) ws[(uint64_t)(24 + w) * n + i] = tv_h_word(m, w, hsrc, Hcache, cstride, Hc, n_msgs);
+  if (astatus[i] != HIPBLS_OK)
+    vstatus[i] = astatus[i];
+  else if (vstatus[i] == RLC_PENDING && agg_inf[i])
+    vstatus[i] = HIPBLS_ERR_VERIFY;
+}
+
+// The lone route's gather (between k_tv_prep8_keys and k_tv_pair_lq16, which does the join itself), one lane per word
+// of a group's H(m); an index out of range is ERR_ARG.  after = 1: launched once more behind k_tv_pair_lq16 by the
+// _device call, only to make that ERR_ARG stand where the aggregation failed too.
+__global__ void __launch_bounds__(kBlock) k_tv_gather_keys(uint64_t n, const uint32_t* __restrict__ key_idx,
+                                                           uint64_t T, const uint32_t* __restrict__ msg_idx,
+                                                           uint64_t n_msgs, const uint32_t* __restrict__ hsrc,
+                                                           const uint32_t* __restrict__ Hcache, uint64_t cstride,
+                                                           const uint32_t* __restrict__ Hc,
+                                                           int32_t* __restrict__ vstatus, uint32_t* __restrict__ ws,
+                                                           uint32_t after) {
+  const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t i = t / 48;
+  const int w = (int)(t % 48);
+  if (i >= n) return;
+  const uint32_t m = msg_idx[i];
+  if (key_idx[i] >= T || m >= n_msgs) {
+    if (w == 0) vstatus[i] = HIPBLS_ERR_ARG;
+    return;
+  }
+  if (!after) ws[(uint64_t)(24 + w) * n + i] = tv_h_word(m, w, hsrc, Hcache, cstride, Hc, n_msgs);
+}
+
 // sigagg's pairing check on lane quads beside [L^-1] S (roles per workgroup, uniform): workgroups [0, grid_for(4 n))
 // run k_verify_pair_lq4's lanes, the rest k_tagg_unscale's.  Both only read ws.
 __global__ void __launch_bounds__(kBlock) k_tv_check_unscale(const uint32_t* __restrict__ ws, uint64_t n,

@@ -228,6 +228,21 @@ BLS_HD BLS_INLINE int pubtab_get(g1a& pk, g1j& xpk, uint64_t k, uint64_t T, cons
   return code[k];
 }
 
+// sigagg's key role with the group's root key named by table index (kernels.h k_tv_phase_a_keys, verify_lat.hip
+// k_tv_prep8_keys): the status k_tv_prep_pk gives the same key's wire bytes -- ERR_PUBKEY for an entry that failed to
+// load, ERR_VERIFY for the infinity key, else pending with lpk = [L] pk for the group's t ids -- without the
+// decompression and subgroup test, which the table load did once.  An index outside the table is ERR_ARG.
+BLS_HD BLS_INLINE int tv_key_lane(g1a& lpk, uint64_t k, uint64_t T, const int32_t* code, const uint32_t* tab,
+                                  const int64_t* ids, int t) {
+  if (k >= T) return HIPBLS_ERR_ARG;
+  g1j xpk;
+  const int dp = pubtab_get(lpk, xpk, k, T, code, tab);
+  if (dp == DEC_BAD) return HIPBLS_ERR_PUBKEY;
+  if (dp == DEC_INF) return HIPBLS_ERR_VERIFY;
+  g1_scale_affine(lpk, tagg_group_L(ids, t));
+  return RLC_PENDING;
+}
+
 // tbls.Verify with the public key taken from the table (same statuses as op_verify); the Miller loop's f in LDS.
 template <int S>
 BLS_HD BLS_CALL int op_verify_decoded_pk(int dp, const g1a& pk, const uint8_t* msg, uint32_t msg_len,

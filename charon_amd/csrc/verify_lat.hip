@@ -239,6 +239,59 @@ __global__ void __launch_bounds__(kOctBlock) k_tv_prep8(const uint8_t* __restric
   if (lead) vstatus[i] = st;
 }
 
+// k_tv_prep8 for the call with keys by table index (hipbls_threshold_aggregate_verify_batch_keys; kernels.h has the
+// data layout): the key blocks read the group's root key from the resident table (rlc.h tv_key_lane: status and
+// [L] pk, the lead lane stores), the hash blocks take one octet per message of the miss list (mlist, or 0 .. n_hash - 1
+// without one) and write H(m) into column m of the call's own table Hc (stride n_msgs), the partial blocks are
+// unchanged.  ws gets [L] pk only: kernels.h k_tv_gather_keys copies each group's H(m) in behind this kernel.  Not
+// raced.
+__global__ void __launch_bounds__(kOctBlock) k_tv_prep8_keys(
+    const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+    const uint32_t* __restrict__ tab, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ moffs,
+    const uint32_t* __restrict__ mlist, uint64_t n_hash, uint64_t n_msgs, uint32_t* __restrict__ Hc, uint64_t G,
+    const int64_t* __restrict__ ids, const uint64_t* __restrict__ goffs, uint32_t* __restrict__ ws,
+    int32_t* __restrict__ vstatus, const uint8_t* __restrict__ sigs, uint64_t n_parts, uint32_t* __restrict__ pts,
+    int32_t* __restrict__ pstat) {
+  bls_race::init(nullptr, 0u);
+  const uint64_t nbg = (8 * G + kOctBlock - 1) / kOctBlock, nbh = (8 * n_hash + kOctBlock - 1) / kOctBlock;
+  uint64_t b = blockIdx.x;
+  int role = 0;  // 0 key, 1 hash, 2 partial: uniform per workgroup
+  if (b >= nbg) {
+    b -= nbg;
+    role = b < nbh ? 1 : 2;
+    if (role == 2) b -= nbh;
+  }
+  const uint64_t t = b * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t i = t >> 3;
+  const bool lead = (t & 7) == 0;
+  if (role == 2) {
+    if (i >= n_parts) return;  // the same on all eight lanes
+    tagg_scale_octet(i, (int)(t & 3), lead, sigs, ids, goffs, G, n_parts, pts, pstat);
+    return;
+  }
+  if (role == 1) {
+    if (i >= n_hash) return;
+    const uint32_t m = (t & 1) ? ~0u : 0u;
+    const uint64_t msg = mlist ? mlist[i] : i;
+    const uint64_t o0 = moffs[msg], o1 = moffs[msg + 1];
+    g2j sum, hj;
+    hash_to_g2_pair_sum(sum, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, m);
+    g2_clear_cofactor_quad(hj, sum, (int)(t & 3));
+    g2a hm;
+    jac_to_aff(hm, hj);
+    if (lead) soa_store<48>(Hc, n_msgs, msg, &hm.x.c0.v[0]);
+    return;
+  }
+  if (i >= G) return;
+  const uint64_t g0 = goffs[i], g1 = goffs[i + 1];
+  g1a pk;
+  const int st = tv_key_lane(pk, key_idx[i], T, tcode, tab, ids + g0, (int)(g1 - g0));
+  if (lead) {
+    if (st == RLC_PENDING) soa_store<24>(ws, G, i, &pk.x.v[0]);
+    vstatus[i] = st;
+  }
+}
+
 // The aggregate-only lone route's stage 2 (hipbls.hip launch_tagg), one workgroup per group, lanes 0-7: the status
 // and the sum S of the scaled partials, then sigma = [L^-1] S compressed (tagg_lat.h).  Bytes and statuses as
 // k_tagg_sum's.

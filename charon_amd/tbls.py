@@ -77,6 +77,10 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
                                                     ctypes.c_int),
         "hipbls_threshold_aggregate_verify_batch_device": ([vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp],
                                                            ctypes.c_int),
+        "hipbls_threshold_aggregate_verify_batch_keys": ([u8p, i64p, u64p, u64, u32p, u32p, u8p, u64p, u64, u8p, i32p,
+                                                          i32p], ctypes.c_int),
+        "hipbls_threshold_aggregate_verify_batch_keys_device": ([vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp,
+                                                                 vp, vp], ctypes.c_int),
         "hipbls_rlc_batch_stats": ([u64p, u64p, i32p], ctypes.c_int),
         "hipbls_verify": ([u8p, u8p, u64, u8p, i32p], ctypes.c_int),
         "hipbls_verify_submit": ([u8p, u8p, u64, u8p, u64p], ctypes.c_int),
@@ -152,6 +156,7 @@ def exported_symbols() -> List[str]:
         "hipbls_plan_ranges", "hipbls_queue_keyed_batches", "hipbls_deserialize_status", "hipbls_device_streams",
         "hipbls_rlc_set_g1_msm_min", "hipbls_scratch_budget", "hipbls_stream_joins", "hipbls_kernel_names",
         "hipbls_queue_worker_stats", "hipbls_set_latency_replicas", "hipbls_build_id",
+        "hipbls_threshold_aggregate_verify_batch_keys", "hipbls_threshold_aggregate_verify_batch_keys_device",
     ]
 
 
@@ -487,6 +492,45 @@ class HipBLS:
         vst = _status_array(n_groups)
         _check(self.lib.hipbls_threshold_aggregate_verify_batch(b"".join(sigs), arr, offs, n_groups, b"".join(dv_pks),
                                                                 blob, moffs, out, ast, vst), self.lib)
+        res = []
+        raw = out.raw
+        for g in range(n_groups):
+            if ast[g] == OK:
+                res.append(raw[96 * g:96 * g + 96])
+            elif ast[g] == ERR_SIGNATURE:
+                res.append(TBLSError("cannot unmarshal signature into Herumi signature"))
+            else:
+                res.append(TBLSError("cannot combine signatures"))
+        return res, list(vst)[:n_groups]
+
+    def batch_threshold_aggregate_verify_keys(self, groups: Sequence[Mapping[int, bytes]],
+                                              dv_key_idx: Sequence[int], msgs: Sequence[bytes],
+                                              msg_idx: Sequence[int]):
+        """batch_threshold_aggregate_verify with dv_pks[g] = loaded table[dv_key_idx[g]] (load_pubshares) and group g's
+        message = msgs[msg_idx[g]]; msgs are the call's DISTINCT messages, each read from the H(m) cache or hashed
+        once.  Same return value."""
+        n_groups = len(groups)
+        if not (len(dv_key_idx) == len(msg_idx) == n_groups):
+            raise ValueError("mismatching lengths")
+        offs = (ctypes.c_uint64 * (n_groups + 1))()
+        ids, sigs = [], []
+        for g, grp in enumerate(groups):
+            offs[g] = len(ids)
+            for idx, sg in grp.items():
+                if len(sg) != 96:
+                    raise ValueError("bad signature length")
+                ids.append(_go_int(idx))
+                sigs.append(bytes(sg))
+        offs[n_groups] = len(ids)
+        arr = (ctypes.c_int64 * max(len(ids), 1))(*ids)
+        blob, moffs = _offsets([bytes(m) for m in msgs])
+        kidx = (ctypes.c_uint32 * max(n_groups, 1))(*dv_key_idx)
+        midx = (ctypes.c_uint32 * max(n_groups, 1))(*msg_idx)
+        out = ctypes.create_string_buffer(96 * max(n_groups, 1))
+        ast = _status_array(n_groups)
+        vst = _status_array(n_groups)
+        _check(self.lib.hipbls_threshold_aggregate_verify_batch_keys(b"".join(sigs), arr, offs, n_groups, kidx, midx,
+                                                                     blob, moffs, len(msgs), out, ast, vst), self.lib)
         res = []
         raw = out.raw
         for g in range(n_groups):

@@ -10,6 +10,11 @@ device sync and the copy-back, so the host clock covers the whole call):
 One process per run; the library comes from HIPBLS_LIB as charon_amd/tbls.py allows (an A/B against another commit's
 build is two processes).  After the clocked pass, a second pass with hipbls_set_timing(1) reports the per-kernel
 averages of the stages the shapes launched.  Prints one JSON object.
+
+The sigagg_keys_* shapes are the same duties through hipbls_threshold_aggregate_verify_batch_keys: the root keys in the
+resident table, the H(m) cache enabled and warmed by one keyed RLC BatchVerify over the duty's partials (what parsigex
+has done by the time charon aggregates); sigagg_keys_7of10_nocache runs with cache capacity 0, so the call hashes the
+root itself.
 """
 import argparse
 import ctypes
@@ -25,18 +30,22 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 R_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 STAGES = ("verify_prep8", "verify_pair_lq16", "verify_pair_lq8", "fav_prep8", "fav_lq16", "fav", "tv_prep8", "tv_lq16",
           "tagg_sum8", "tv_phase_a", "tv_prep_pk", "tagg_scale", "tagg_sum", "tv_check_unscale", "tagg_unscale",
-          "verify_pair_lq4", "verify_pair_lg2")
+          "verify_pair_lq4", "verify_pair_lg2", "tv_prep8_keys", "tv_gather_keys", "tv_phase_a_keys")
 
 
 def _duty(impl, rng, t, total):
-    """One validator's duty: t of its `total` partials, its root key and its 32-byte signing root."""
+    """One validator's duty: t of its `total` partials, its root key, its 32-byte signing root and Sign(secret); and
+    the pubshares of those partials by id."""
     secret = rng.randrange(1, R_ORDER).to_bytes(32, "big")
     msg = rng.randbytes(32)
     shares = impl.threshold_split(secret, total, t)
     ids = sorted(rng.sample(range(1, total + 1), t))
     sigs, st = impl.sign_batch([shares[i] for i in ids], [msg] * t)
     assert set(st) == {0}
-    return dict(zip(ids, sigs)), impl.secret_to_public_key(secret), msg, impl.sign(secret, msg)
+    pubshares, st = impl.secret_to_public_key_batch([shares[i] for i in ids])
+    assert set(st) == {0}
+    return (dict(zip(ids, sigs)), impl.secret_to_public_key(secret), msg, impl.sign(secret, msg)), \
+        (dict(zip(ids, pubshares)), ids)
 
 
 def _fav(impl, rng, nkeys):
@@ -65,7 +74,8 @@ def main():
     from charon_amd import tbls
     impl = tbls.HipBLS()
     rng = random.Random(0x10E)
-    d46, d710, d710b = _duty(impl, rng, 4, 6), _duty(impl, rng, 7, 10), _duty(impl, rng, 7, 10)
+    made = [_duty(impl, rng, 4, 6), _duty(impl, rng, 7, 10), _duty(impl, rng, 7, 10)]
+    (d46, d710, d710b), shares = [m[0] for m in made], [m[1] for m in made]
     fav4, fav12 = _fav(impl, rng, 4), _fav(impl, rng, 12)
 
     def verify(d):  # a Verify of the duty's aggregate: the randao / block signature check
@@ -87,15 +97,54 @@ def main():
         verify(d710b)
         sigagg(d710b)
 
+    # the keyed shapes: table = each duty's pubshares (for the warm-up RLC call) and root key
+    duties = (d46, d710, d710b)
+    table, root_idx, share_idx = [], [], []
+    for d, (sh, _) in zip(duties, shares):
+        share_idx.append({i: len(table) + k for k, i in enumerate(sorted(sh))})
+        table.extend(sh[i] for i in sorted(sh))
+        root_idx.append(len(table))
+        table.append(d[1])
+    assert set(impl.load_pubshares(table)) == {0}
+
+    def warm(k):  # parsigex's keyed RLC BatchVerify over the duty's partials: caches H(root)
+        d = duties[k]
+        ids = list(d[0])
+        st = impl.batch_verify_rlc_keys_status([share_idx[k][i] for i in ids], [d[2]] * len(ids), [d[0][i] for i in ids])
+        assert st == [0] * len(ids)
+
+    def sigagg_keys(k):
+        d = duties[k]
+        aggs, vst = impl.batch_threshold_aggregate_verify_keys([d[0]], [root_idx[k]], [d[2]], [0])
+        assert aggs == [d[3]] and vst == [0]
+
+    def cache(capacity, ks=()):
+        impl.hcache_config(capacity)
+        for k in ks:
+            warm(k)
+
+    def chain_keys():
+        verify(d710)
+        sigagg_keys(1)
+        verify(d710b)
+        sigagg_keys(2)
+
     shapes = [("verify_1", lambda: verify(d710)), ("fav_1x4", lambda: fav(fav4)), ("fav_1x12", lambda: fav(fav12)),
               ("sigagg_4of6", lambda: sigagg(d46)), ("sigagg_7of10", lambda: sigagg(d710)),
-              ("tagg_7of10", lambda: tagg(d710)), ("chain_verify_sigagg_x2", chain)]
-    for _, fn in shapes:
+              ("tagg_7of10", lambda: tagg(d710)), ("chain_verify_sigagg_x2", chain),
+              ("sigagg_keys_4of6", lambda: sigagg_keys(0)), ("sigagg_keys_7of10", lambda: sigagg_keys(1)),
+              ("sigagg_keys_7of10_nocache", lambda: sigagg_keys(1)), ("chain_verify_sigagg_keys_x2", chain_keys)]
+    # the cache state each shape runs in (set before its warm-up and again before its clocked and timed passes)
+    setup = {"sigagg_keys_4of6": lambda: cache(65536, (0,)), "sigagg_keys_7of10": lambda: cache(65536, (1,)),
+             "sigagg_keys_7of10_nocache": lambda: cache(0), "chain_verify_sigagg_keys_x2": lambda: cache(65536, (1, 2))}
+    for name, fn in shapes:
+        setup.get(name, lambda: None)()
         for _ in range(a.warmup):
             fn()
     out = {"lib": os.environ.get("HIPBLS_LIB") or "in-tree", "build_id": tbls.build_id().get("src", "")[:16],
            "calls": a.calls, "warmup": a.warmup, "shapes": {}, "kernels_ms": {}}
     for name, fn in shapes:
+        setup.get(name, lambda: None)()
         ms = []
         for _ in range(a.calls):
             t0 = time.perf_counter()
@@ -106,7 +155,10 @@ def main():
     impl.lib.hipbls_kernel_timing_reset()
     impl.lib.hipbls_set_timing(1)
     try:
-        for name, fn in shapes[:-1]:
+        for name, fn in shapes:
+            if name.startswith("chain_"):
+                continue
+            setup.get(name, lambda: None)()
             impl.lib.hipbls_kernel_timing_reset()
             for _ in range(a.timing_calls):
                 fn()
@@ -119,6 +171,7 @@ def main():
             out["kernels_ms"][name] = per
     finally:
         impl.lib.hipbls_set_timing(0)
+        impl.hcache_config(0)
     print(json.dumps(out, sort_keys=True))
 
 

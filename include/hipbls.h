@@ -300,6 +300,31 @@ int hipbls_threshold_aggregate_verify_batch_device(const uint8_t* d_sigs, const 
 int hipbls_threshold_aggregate_batch_device(const uint8_t* d_sigs, const int64_t* d_share_idx,
                                             const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
                                             uint8_t* d_out_sigs, int32_t* d_status, void* stream);
+/* hipbls_threshold_aggregate_verify_batch with dv_pks[g] = table[dv_key_idx[g]] (the validators' root keys loaded
+ * into the resident table beside the pubshares, hipbls_pubshare_table_load) and message g = message msg_idx[g] of
+ * n_msgs DISTINCT messages, msgs[msg_offsets[m] .. msg_offsets[m+1]) as in hipbls_batch_verify_rlc: an attester
+ * duty's groups share a few roots, and each is hashed at most once.  out_sigs and both status arrays are exactly what
+ * the wire-format call returns for the same key bytes, in every pair mode (a table entry that failed to load:
+ * HIPBLS_ERR_PUBKEY; the infinity key: HIPBLS_ERR_VERIFY).  No key is decompressed or subgroup-tested: the table load
+ * did that once.  Each distinct message is looked up in the context's H(m) cache (hipbls_hcache_config; counted in
+ * hipbls_hcache_stats): a hit -- by sigagg time the RLC BatchVerify of the root's partials has normally cached it --
+ * is read from its column, a miss is hashed once into a table of the call's own, also with the cache disabled.  The
+ * call only reads the cache (sigagg is the last consumer of a root): it never inserts or evicts.  HIPBLS_ERR_ARG for
+ * the whole call when a key index is outside the table or a message index is >= n_msgs.  Routes and kernels as the
+ * wire-format call's, timed as tv_prep8_keys + tv_gather_keys + tv_lq16 (lone) and tv_phase_a_keys (throughput). */
+int hipbls_threshold_aggregate_verify_batch_keys(const uint8_t* sigs, const int64_t* share_idx,
+                                                 const uint64_t* group_offsets, uint64_t n_groups,
+                                                 const uint32_t* dv_key_idx, const uint32_t* msg_idx,
+                                                 const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t n_msgs,
+                                                 uint8_t* out_sigs, int32_t* agg_status, int32_t* verify_status);
+/* Device variant: the host never sees the messages, so every distinct message is hashed once into the call's own
+ * table and the H(m) cache is untouched.  An out-of-range key or message index yields verify_status[g] =
+ * HIPBLS_ERR_ARG, also where the group's aggregation failed; agg_status[g] and out_sigs are the aggregation's. */
+int hipbls_threshold_aggregate_verify_batch_keys_device(
+    const uint8_t* d_sigs, const int64_t* d_share_idx, const uint64_t* d_group_offsets, uint64_t n_groups,
+    uint64_t n_parts, const uint32_t* d_dv_key_idx, const uint32_t* d_msg_idx, const uint8_t* d_msgs,
+    const uint64_t* d_msg_offsets, uint64_t n_msgs, uint8_t* d_out_sigs, int32_t* d_agg_status,
+    int32_t* d_verify_status, void* stream);
 int hipbls_aggregate_device(const uint8_t* d_sigs, uint64_t n, uint8_t* d_out_sig, int32_t* d_status, void* stream);
 int hipbls_sign_batch_device(const uint8_t* d_sks, const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
                              uint64_t n, uint8_t* d_out_sigs, int32_t* d_status, void* stream);
@@ -329,7 +354,8 @@ int hipbls_batch_verify_rlc_keys_device(const uint32_t* d_key_idx, const uint8_t
  * events on the stream it runs on (bench.py roofline; enable with hipbls_set_timing).  Names: "verify"
  * (k_verify_fused), "verify_prep" + "verify_pair_lg2" (lane-pair Verify), "verify_keys", "rlc_items",
  * "rlc_hash", "rlc_window" / "rlc_window_lg2", "rlc_fallback" / "rlc_fallback_lg2", "tagg_scale", "tagg_sum",
- * "fav". */
+ * "fav"; sigagg in one call: "tv_phase_a", "tv_check_unscale", "tv_prep8", "tv_lq16", and with keys by index
+ * "tv_phase_a_keys", "tv_prep8_keys", "tv_gather_keys". */
 int hipbls_kernel_timing(const char* name, double* avg_ms, uint64_t* launches);
 int hipbls_kernel_timing_reset(void);
 

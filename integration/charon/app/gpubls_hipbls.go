@@ -19,6 +19,11 @@ func selectGPUBLS(ctx context.Context) error {
 	if err != nil {
 		return err
 	}
+	// The resident H(m) cache: a signing root is hashed to G2 when its first partials are verified (parsigex,
+	// validatorapi) and read again by every later batch of that root and by sigagg.
+	if err := hipbls.ConfigHCache(hipbls.DefaultHCacheCapacity); err != nil {
+		return err
+	}
 	tbls.SetImplementation(impl)
 	log.Info(ctx, "tbls backed by the GPU implementation", z.Str("impl", "hipbls"))
 

@@ -198,6 +198,10 @@ func (h HipBLS) BatchVerifyAggregate(keys [][]tbls.PublicKey, sigs []tbls.Signat
 // of its partials (or the aggregation error) and the error Verify(dvPks[g], msgs[g], aggregate) would return (the
 // aggregation's error when it failed).  Same results as BatchThresholdAggregate + BatchVerify; the root key decode
 // and H(m) run beside the aggregation and the aggregate is not decompressed again (DESIGN.md 4.9).
+//
+// With sigaggByKeys set and every root key in the resident table (app.go loads them beside the pubshares) the call
+// names them by index and passes the DISTINCT roots: no key decode or subgroup test, each root read from the H(m) cache
+// that the RLC BatchVerify of its partials filled, or hashed once (DESIGN.md 4.9.1).  Otherwise the wire-format call.
 func (HipBLS) BatchThresholdAggregateVerify(groups []map[int]tbls.Signature, dvPks []tbls.PublicKey,
 	msgs [][]byte,
 ) ([]tbls.Signature, []error, []error, error) {
@@ -209,15 +213,32 @@ func (HipBLS) BatchThresholdAggregateVerify(groups []map[int]tbls.Signature, dvP
 		return nil, nil, nil, errors.New("mismatching lengths")
 	}
 	sigs, ids, offs := groupsFlat(groups)
-	flat, moffs := flatten(msgs)
 	out := make([]tbls.Signature, n)
 	ast := make([]int32, n)
 	vst := make([]int32, n)
-	rc := C.hipbls_threshold_aggregate_verify_batch(u8(sigs), i64(ids), u64(offs), C.uint64_t(n),
-		(*C.uint8_t)(unsafe.Pointer(&dvPks[0][0])), u8(flat), u64(moffs), (*C.uint8_t)(unsafe.Pointer(&out[0][0])),
-		i32(ast), i32(vst))
+	var rc C.int
+	path := "fused_sigagg"
+	var kidx []uint32
+	keyed, release := false, func() {}
+	if sigaggByKeys {
+		kidx, keyed, release = lockTable(dvPks) // held across the call, as in BatchVerify
+	}
+	if keyed {
+		path = "batch_threshold_aggregate_verify_keys"
+		roots, midx := distinctRoots(msgs)
+		flat, moffs := flatten(roots)
+		rc = C.hipbls_threshold_aggregate_verify_batch_keys(u8(sigs), i64(ids), u64(offs), C.uint64_t(n),
+			(*C.uint32_t)(unsafe.Pointer(&kidx[0])), (*C.uint32_t)(unsafe.Pointer(&midx[0])), u8(flat), u64(moffs),
+			C.uint64_t(len(roots)), (*C.uint8_t)(unsafe.Pointer(&out[0][0])), i32(ast), i32(vst))
+	} else {
+		flat, moffs := flatten(msgs)
+		rc = C.hipbls_threshold_aggregate_verify_batch(u8(sigs), i64(ids), u64(offs), C.uint64_t(n),
+			(*C.uint8_t)(unsafe.Pointer(&dvPks[0][0])), u8(flat), u64(moffs), (*C.uint8_t)(unsafe.Pointer(&out[0][0])),
+			i32(ast), i32(vst))
+	}
+	release()
 	if rc != C.HIPBLS_OK {
-		return nil, nil, nil, observeFailure("fused_sigagg", n, devErr(rc))
+		return nil, nil, nil, observeFailure(path, n, devErr(rc))
 	}
 	aggErrs := make([]error, n)
 	verErrs := make([]error, n)
@@ -229,7 +250,33 @@ func (HipBLS) BatchThresholdAggregateVerify(groups []map[int]tbls.Signature, dvP
 			verErrs[g] = verifyErr(vst[g], dvPks[g][:], out[g][:])
 		}
 	}
-	observe("fused_sigagg", verErrs)
+	observe(path, verErrs)
 
 	return out, aggErrs, verErrs, nil
+}
+
+// sigaggByKeys: BatchThresholdAggregateVerify takes the keyed call when every root key is resident.  Results are the
+// same either way, so the default rests on the measured times (DESIGN.md 4.9.1, profiles/r08): the keyed call with a
+// warm cache is 1.0 ms faster on a lone 7-of-10 duty (9.1 against 10.1 ms p50), but 2-3 % slower on 10,000 validators
+// with 10,000 distinct roots from two threads (its cache lookups run on the host under the context lock, and the
+// hashes they save were hidden beside the partials' scaling anyway), so the wire-format call stays the default.
+var sigaggByKeys = false
+
+// distinctRoots dedupes the groups' messages (an attester duty's validators share one root per committee) into the
+// distinct-message table of the keyed call: roots in first-use order and each group's index into them.
+func distinctRoots(msgs [][]byte) ([][]byte, []uint32) {
+	pos := make(map[string]uint32, len(msgs))
+	var roots [][]byte
+	midx := make([]uint32, len(msgs))
+	for g, m := range msgs {
+		j, ok := pos[string(m)]
+		if !ok {
+			j = uint32(len(roots))
+			pos[string(m)] = j
+			roots = append(roots, m)
+		}
+		midx[g] = j
+	}
+
+	return roots, midx
 }

@@ -119,6 +119,21 @@ func ScratchBudget(d int) (Scratch, error) {
 	return Scratch{PerLane: uint64(pl), PerQueue: uint64(pq), Limit: uint64(lim), Queues: uint32(q)}, nil
 }
 
+// DefaultHCacheCapacity is the H(m) cache's size in columns of 192 bytes: 65,536 columns are 12 MiB per GPU
+// (INTEGRATION.md "Start-up" says how to size it).
+const DefaultHCacheCapacity = 65536
+
+// ConfigHCache sets the capacity of every GPU's resident H(m) cache (hipbls_hcache_config): each distinct signing root
+// the RLC BatchVerify sees is hashed to G2 once and kept, and BatchThresholdAggregateVerify reads it from there.
+// 0 disables the cache.  Results are unchanged by it.
+func ConfigHCache(capacity uint64) error {
+	if rc := C.hipbls_hcache_config(C.uint64_t(capacity)); rc != C.HIPBLS_OK {
+		return devErr(rc)
+	}
+
+	return nil
+}
+
 // LoadPubShares decodes and subgroup-checks the cluster's pubshares once into every GPU's resident table
 // (hipbls_pubshare_table_load; SURVEY.md §8f.2: the lock's keys, app/app.go:344-381).  Afterwards BatchVerify and
 // BatchVerifyRLC name keys by table index when every key of a call is in the table (no per-call decode or subgroup
