@@ -50,13 +50,14 @@ extern "C" {
 __global__ void k_rlc_items(uint64_t i0, uint64_t i1, const uint8_t* pks, const uint8_t* sigs, const uint32_t* msg_idx,
                             uint64_t n, uint64_t n_msgs, bls::rlc_seed seed, uint32_t* rpk, uint32_t* rsig,
                             int32_t* status, const uint32_t* key_idx, uint64_t T, const int32_t* tcode,
-                            const uint32_t* tab);
+                            const uint32_t* tab, bls::keycache kc);
 __global__ void k_rlc_hash(const uint8_t* msgs, const uint64_t* offs, uint64_t n_hash, const uint32_t* mlist, uint32_t* H,
                            uint64_t hstride, const uint32_t* hslot);
 __global__ void k_rlcb_items(uint64_t n, const uint8_t* pks, const uint8_t* sigs, const uint32_t* msg_idx,
                              uint64_t n_msgs, bls::rlc_seed seed, uint32_t* rpk, uint32_t* pts, uint32_t* sc,
                              int32_t* status, const uint32_t* key_idx, uint64_t T, const int32_t* tcode,
-                             const uint32_t* tab, const uint32_t* g1pos, uint32_t* gpts, uint32_t* gsc);
+                             const uint32_t* tab, const uint32_t* g1pos, uint32_t* gpts, uint32_t* gsc,
+                             bls::keycache kc);
 }
 
 // The eight-lane latency path (verify_lat.hip, its own translation unit: BLS_FP2_PAIR build in namespace bls_fp2p).
@@ -150,6 +151,34 @@ struct HCache {
   DevBuf table;
   uint64_t hits = 0, misses = 0;
 };
+
+// Resident key cache (keycache.h): wire bytes of a public key -> its decoded form, filled and
+// read by the wire-format Verify and RLC kernels themselves.  The host only owns the buffers: it zeroes them
+// (hipbls_keycache_config) and reads the counters.
+// `mu` guards the four fields against hipbls_keycache_config: every launch of a kernel that takes the cache copies the
+// struct and enqueues the kernel with `mu` held (KC_LAUNCH_GUARD), and config holds it from before it waits for the
+// device until the new buffers are zeroed.  The context lock does not do: the submission queue's worker launches wire
+// batches without it.  So no kernel is ever enqueued with pointers that config has freed or with half of a new struct.
+// Lock order: the context's mu (where held), then this one.
+struct KeyCache {
+  std::mutex mu;
+  uint64_t slots = 0;  // power of two; 0 = off
+  uint32_t* entries = nullptr;
+  uint32_t* claim = nullptr;
+  unsigned long long* ctr = nullptr;  // hits, misses, inserts
+  bls::keycache dev() const {
+    bls::keycache k{};
+    if (slots) {
+      k.entries = entries;
+      k.claim = claim;
+      k.ctr = ctr;
+      k.mask = (uint32_t)(slots - 1);
+    }
+    return k;
+  }
+};
+constexpr uint64_t kKeyCacheDefaultSlots = 65536;  // x 256 B = 16 MiB per context; a cluster's 4,096 pubshares load it to 6 %
+constexpr uint64_t kKeyCacheMaxSlots = 1ull << 24;
 
 // One open or running batch of the submission queue.
 struct VBatch {
@@ -281,6 +310,7 @@ struct Context {
   int rlcb_skipped = 0;                 // AUTO: calls run windows-only since the last failed batch check
   uint64_t rlcb_attempted = 0, rlcb_passed = 0;
   HCache hcache;
+  KeyCache kcache;
   std::mutex tmu;                            // timing table (also used by the queue worker)
   std::map<std::string, TimingSlot> timing;  // per kernel name: HIP events on the launch stream
   VerifyQueue q;
@@ -310,6 +340,54 @@ int arg_err(const char* what) {
     hipError_t _e = (expr);                          \
     if (_e != hipSuccess) return set_err(#expr, _e); \
   } while (0)
+
+// (Re)build a context's key cache with `slots` slots (0: off; rounded up to a power of two, at least a probe window),
+// all empty, counters zero.  The context's device is current and nothing of the context runs on it.  The buffers are
+// zeroed on the library stream `s`, never on the null stream: a process's streams share GPU_MAX_HW_QUEUES hardware
+// queues, and a first use of the null stream would take one of them away from the library's own (the RLC sub-batches
+// then queue behind each other instead of overlapping).
+int keycache_setup(KeyCache& kc, uint64_t slots, hipStream_t s) {
+  if (slots > kKeyCacheMaxSlots) return arg_err("key cache above 2^24 slots");
+  uint64_t want = 0;
+  if (slots) {
+    want = bls::KC_MIN_SLOTS;
+    while (want < slots) want <<= 1;
+  }
+  if (want != kc.slots) {
+    if (kc.entries) (void)hipFree(kc.entries);
+    if (kc.claim) (void)hipFree(kc.claim);
+    kc.entries = kc.claim = nullptr;
+    kc.slots = 0;
+    if (want) {
+      HIP_TRY(hipMalloc((void**)&kc.entries, want * bls::KC_WORDS * 4));
+      HIP_TRY(hipMalloc((void**)&kc.claim, want * 4));
+      kc.slots = want;
+    }
+  }
+  if (!kc.ctr) HIP_TRY(hipMalloc((void**)&kc.ctr, 3 * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(kc.ctr, 0, 3 * sizeof(unsigned long long), s));
+  if (kc.slots) {
+    HIP_TRY(hipMemsetAsync(kc.claim, 0, kc.slots * 4, s));
+    HIP_TRY(hipMemsetAsync(kc.entries, 0, kc.slots * bls::KC_WORDS * 4, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  return HIPBLS_OK;
+}
+// HIPBLS_KEYCACHE_SLOTS overrides the default size; 0 turns the cache off.
+uint64_t keycache_default_slots() {
+  const char* e = getenv("HIPBLS_KEYCACHE_SLOTS");
+  if (!e || !e[0]) return kKeyCacheDefaultSlots;
+  char* end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  if (end == e || *end || v > kKeyCacheMaxSlots) {
+    fprintf(stderr, "hipbls: HIPBLS_KEYCACHE_SLOTS=%s ignored (expected 0 .. 2^24)\n", e);
+    return kKeyCacheDefaultSlots;
+  }
+  return (uint64_t)v;
+}
+
+// Held across "copy the cache struct, enqueue the kernel" (KeyCache::mu).
+#define KC_LAUNCH_GUARD(c) std::lock_guard<std::mutex> _kcl((c).kcache.mu)
 
 int nctx() { return g_nctx.load(std::memory_order_acquire); }
 Context& ctx(int k) { return *g_ctxs[k]; }
@@ -534,6 +612,10 @@ int init_locked(const std::vector<int>& ids) {
     if (hipExtStreamGetCUMask(c->stream, kCuMaskWords, c->cu_mask.data()) != hipSuccess) {
       (void)hipGetLastError();
       c->cu_mask.clear();  // no CU-mask query on this runtime: only the priority decides
+    }
+    {
+      const int krc = keycache_setup(c->kcache, keycache_default_slots(), c->stream);
+      if (krc) return krc;
     }
     made.push_back(c);
   }
@@ -939,8 +1021,9 @@ int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const
   if (n == 0) return HIPBLS_OK;
   if (!use_pairs(n, kLg2MaxVerify))
     return timed(c, "verify", s, [&] {
+      KC_LAUNCH_GUARD(c);
       hipLaunchKernelGGL(k_verify_fused, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs,
-                         d_sigs, n, d_status);
+                         d_sigs, n, d_status, c.kcache.dev());
     });
   // + two decode codes per item for the octet path, and the octet path's race words in the buffer's last 64 bytes (a
   // fixed place per allocation, 64-byte aligned since the capacity is a multiple of 256, beyond every batch's data;
@@ -980,8 +1063,9 @@ int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const
   }
   int rc = timed(c, "verify_prep", s, [&] {
     const int pair_hash = n <= kPairHashMaxVerify ? 1 : 0;
+    KC_LAUNCH_GUARD(c);
     hipLaunchKernelGGL(k_verify_prep, dim3((unsigned)((pair_hash ? 3 : 2) * grid_for(n))), dim3(kBlock), 0, s, d_pks,
-                       d_msgs, d_offs, d_sigs, n, (uint32_t*)ws.p, d_status, pair_hash);
+                       d_msgs, d_offs, d_sigs, n, (uint32_t*)ws.p, d_status, pair_hash, c.kcache.dev());
   });
   if (rc) return rc;
   if (use_quads(n))
@@ -1135,8 +1219,9 @@ int launch_rlc(Context& c, const uint8_t* d_pks, const uint8_t* d_sigs, const ui
     const uint64_t i0 = w0 * RLC_W, i1 = w1 * RLC_W < n ? w1 * RLC_W : n;
     HIP_TRY(hipStreamWaitEvent(ss, c.ev_fork, 0));
     rc = timed(c, "rlc_items", ss, [&] {
+      KC_LAUNCH_GUARD(c);
       hipLaunchKernelGGL(k_rlc_items, dim3((unsigned)grid_for(i1 - i0)), dim3(kBlock), 0, ss, i0, i1, d_pks, d_sigs,
-                         d_midx, n, n_msgs, seed, rpk, rsig, d_status, d_kidx, T, tcode, tab);
+                         d_midx, n, n_msgs, seed, rpk, rsig, d_status, d_kidx, T, tcode, tab, c.kcache.dev());
     });
     if (rc) return rc;
     HIP_TRY(hipStreamWaitEvent(ss, c.ev_hash, 0));
@@ -1346,9 +1431,10 @@ int launch_rlc_batch(Context& c, const uint8_t* d_pks, const uint8_t* d_sigs, co
     if (rc) return rc;
   }
   rc = timed(c, "rlcb_items", s0, [&] {
+    KC_LAUNCH_GUARD(c);
     hipLaunchKernelGGL(k_rlcb_items, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s0, n, d_pks, d_sigs, d_midx, n_msgs,
                        seed, rpk, pts, sc, d_status, d_kidx, T, tcode, tab, (const uint32_t*)G(gl.pos), G(gl.pts),
-                       G(gl.sc));
+                       G(gl.sc), c.kcache.dev());
   });
   if (rc) return rc;
   HIP_TRY(hipEventRecord(c.rlcb_ev_items, s0));
@@ -3321,6 +3407,38 @@ int hipbls_hcache_config(uint64_t capacity) {
     if (capacity) HIP_TRY(hc.table.ensure(capacity * 48 * 4));
     return HIPBLS_OK;
   });
+}
+
+int hipbls_keycache_config(uint64_t slots) {
+  if (slots > kKeyCacheMaxSlots) return arg_err("key cache above 2^24 slots");
+  ENSURE_INIT();
+  return run_all([&](Context& c) -> int {
+    // the context lock (run_all) keeps the library-stream callers out, the cache's own lock the queue worker's wire
+    // launches: from here on no kernel is enqueued with this cache until the new buffers stand
+    KC_LAUNCH_GUARD(c);
+    HIP_TRY(hipDeviceSynchronize());  // every kernel enqueued so far, on every stream, is done with the old buffers
+    return keycache_setup(c.kcache, slots, c.stream);
+  });
+}
+
+int hipbls_keycache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts) {
+  if (!hits || !misses || !inserts) return arg_err("null output");
+  *hits = *misses = *inserts = 0;
+  ENSURE_INIT();
+  const int n = nctx();
+  for (int k = 0; k < n; ++k) {
+    Context& c = ctx(k);
+    ENTER_CTX(c);
+    if (!c.kcache.ctr) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    HIP_TRY(hipDeviceSynchronize());  // the counters of every call that has been enqueued
+    HIP_TRY(hipMemcpyAsync(v, c.kcache.ctr, sizeof(v), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    *hits += v[0];
+    *misses += v[1];
+    *inserts += v[2];
+  }
+  return HIPBLS_OK;
 }
 
 int hipbls_hcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries) {

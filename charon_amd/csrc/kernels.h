@@ -27,13 +27,14 @@ __global__ void __launch_bounds__(kBlock) k_verify_fused(const uint8_t* __restri
                                                          const uint8_t* __restrict__ msgs,
                                                          const uint64_t* __restrict__ offs,
                                                          const uint8_t* __restrict__ sigs, uint64_t n,
-                                                         int32_t* __restrict__ status) {
+                                                         int32_t* __restrict__ status, keycache kc) {
   const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t o0 = offs[i], o1 = offs[i + 1];
 #if BLS_VERIFY_LDS
   BLS_LANE_F12(F);
-  status[i] = op_verify_l_kernel(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i, F);
+  // the key's decode goes through the key cache (keycache.h; kc.entries == nullptr: off)
+  status[i] = op_verify_l_kernel_kc(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i, F, kc);
 #else
   status[i] = op_verify(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i);
 #endif
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(kBlock) k_verify_prep(const uint8_t* __restric
                                                         const uint64_t* __restrict__ offs,
                                                         const uint8_t* __restrict__ sigs, uint64_t n,
                                                         uint32_t* __restrict__ ws, int32_t* __restrict__ status,
-                                                        int pair_hash) {
+                                                        int pair_hash, keycache kc) {
   const uint64_t nb = (n + kBlock - 1) / kBlock;
   const bool hash_role = blockIdx.x >= nb;  // uniform per workgroup
   if (hash_role && pair_hash) {  // lanes 2i, 2i+1 hash item i together (lg2.h hash_to_g2_pair)
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(kBlock) k_verify_prep(const uint8_t* __restric
   g1a pk;
   g2a sig;
   int st = RLC_PENDING;
-  const int dp = g1_decompress(pk, pks + 48 * i, true);
+  const int dp = g1_decode_kc_pk(pk, pks + 48 * i, kc);  // through the key cache (keycache.h)
   if (dp == DEC_BAD) {
     st = HIPBLS_ERR_PUBKEY;
   } else {

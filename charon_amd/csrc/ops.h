@@ -296,12 +296,12 @@ BLS_HD BLS_CALL int op_verify(const uint8_t* pk48, const uint8_t* msg, uint32_t 
   return pairing_check_verify_sig(pk, hm, sig);
 }
 
-// op_verify with the Miller loop's f in LDS (F: this lane's slot; pairing_lds.h).
+// op_verify with the Miller loop's f in LDS (F: this lane's slot; pairing_lds.h), in two parts: the key's decode
+// (dp: its DEC_* code with the subgroup test included) and the rest, so that a key served by the key cache (rlc.h
+// op_verify_l_kernel_kc) joins the same chain as one decoded here.
 template <int S, bool INL>
-BLS_HD BLS_INLINE int op_verify_l_body(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len, const uint8_t* sig96,
-                                     const f12l<S> F) {
-  g1a pk;
-  const int dp = g1_decompress(pk, pk48, true);
+BLS_HD BLS_INLINE int op_verify_l_rest(int dp, const g1a& pk, const uint8_t* msg, uint32_t msg_len,
+                                       const uint8_t* sig96, const f12l<S> F) {
   if (dp == DEC_BAD) return HIPBLS_ERR_PUBKEY;
   g2a sig;
   const int ds = g2_decompress(sig, sig96, false);
@@ -312,6 +312,13 @@ BLS_HD BLS_INLINE int op_verify_l_body(const uint8_t* pk48, const uint8_t* msg, 
   g2a hm;
   jac_to_aff(hm, hj);
   return pairing_check_verify_sig_l_body<S, INL>(pk, hm, sig, F);
+}
+template <int S, bool INL>
+BLS_HD BLS_INLINE int op_verify_l_body(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len, const uint8_t* sig96,
+                                     const f12l<S> F) {
+  g1a pk;
+  const int dp = g1_decompress(pk, pk48, true);
+  return op_verify_l_rest<S, INL>(dp, pk, msg, msg_len, sig96, F);
 }
 template <int S>
 BLS_HD BLS_VERIFY_L_CALL int op_verify_l(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len, const uint8_t* sig96,

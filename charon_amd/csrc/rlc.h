@@ -16,6 +16,7 @@
 //   G2: [r] sig = [a] sig + [b] psi(sig)       (psi = [x] on G2, curve.h g2_in_subgroup)
 //   G1: [r] pk  = [a] pk  + [b] ([x] pk)       ([x] pk is the first half of the G1 subgroup test)
 #pragma once
+#include "keycache.h"
 #include "ops.h"
 
 namespace bls {
@@ -152,6 +153,42 @@ BLS_HD BLS_CALL int g1_decompress_keep_x(g1a& out, g1j& xP, const uint8_t* b) {
   return DEC_OK;
 }
 
+// The same decode behind the key cache (keycache.h): a hit takes y (and, WANT_X, [x] P) from the entry and x from the
+// wire bytes, and skips the square root and the subgroup test; a miss decodes as above and publishes a DEC_OK result.
+// Only DEC_OK keys are ever entries, so every other key takes the miss path each time and its code is unchanged.
+template <bool WANT_X>
+BLS_HD BLS_INLINE int g1_decode_kc_body(g1a& out, g1j& xP, const uint8_t* b, const keycache& kc) {
+  uint32_t tag[12];
+  kc_tag_from_wire(tag, b);
+  int st;
+  bool ins = false;
+  const bool hit = kc_lookup(kc, tag, out.y.v, WANT_X ? &xP.x.v[0] : nullptr);
+  if (hit) {
+    uint8_t buf[48];
+    for (int i = 0; i < 48; ++i) buf[i] = b[i];
+    buf[0] &= 0x1f;
+    fp_plain_from_be48(out.x, buf);
+    fp_to_mont(out.x, out.x);
+    st = DEC_OK;
+  } else {
+    st = g1_decompress_keep_x(out, xP, b);
+    if (st == DEC_OK) ins = kc_insert(kc, tag, out.y.v, &xP.x.v[0]);
+  }
+  kc_count(kc, hit, ins);
+  return st;
+}
+// for the RLC item stages: the key and [x] P
+BLS_HD BLS_CALL int g1_decode_kc_x(g1a& out, g1j& xP, const uint8_t* b, const keycache& kc) {
+  if (!kc.entries) return g1_decompress_keep_x(out, xP, b);
+  return g1_decode_kc_body<true>(out, xP, b, kc);
+}
+// for Verify: the key alone (cache off: g1_decompress with its subgroup test, as before the cache)
+BLS_HD BLS_CALL int g1_decode_kc_pk(g1a& out, const uint8_t* b, const keycache& kc) {
+  if (!kc.entries) return g1_decompress(out, b, true);
+  g1j xP;
+  return g1_decode_kc_body<false>(out, xP, b, kc);
+}
+
 // Stage 1 with the public key already decoded: dp = its DEC_* code, pk affine, xpk = [x] pk (from
 // g1_decompress_keep_x, either just now or once at load time in the resident pubshare table).
 // Decodes + subgroup-checks the signature in herumi's order, then stores [r_i] pk_i (G1 Jacobian,
@@ -202,6 +239,13 @@ BLS_HD BLS_CALL int rlc_item(const uint8_t* pk48, const uint8_t* sig96, const rl
   const int dp = g1_decompress_keep_x(pk, xpk, pk48);
   return rlc_item_decoded(dp, pk, xpk, sig96, seed, i, rpk36, rsig72);
 }
+BLS_HD BLS_CALL int rlc_item_kc(const uint8_t* pk48, const uint8_t* sig96, const rlc_seed& seed, uint64_t i,
+                                uint32_t* rpk36, uint32_t* rsig72, const keycache& kc) {
+  g1a pk;
+  g1j xpk;
+  const int dp = g1_decode_kc_x(pk, xpk, pk48, kc);
+  return rlc_item_decoded(dp, pk, xpk, sig96, seed, i, rpk36, rsig72);
+}
 
 // ---- resident pubshare table: every pubshare decoded + subgroup-checked once ----
 // SoA with stride T (table size): code[T] (DEC_*), then 24 words affine (x, y), then 36 words [x]pk.
@@ -241,6 +285,16 @@ BLS_HD BLS_INLINE int tv_key_lane(g1a& lpk, uint64_t k, uint64_t T, const int32_
   if (dp == DEC_INF) return HIPBLS_ERR_VERIFY;
   g1_scale_affine(lpk, tagg_group_L(ids, t));
   return RLC_PENDING;
+}
+
+// k_verify_fused's form (ops.h op_verify_l_kernel) with the key decode behind the key cache: a hit and a miss join
+// the same kernel-inlined chain.
+template <int S>
+BLS_HD BLS_INLINE int op_verify_l_kernel_kc(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len,
+                                            const uint8_t* sig96, const f12l<S> F, const keycache& kc) {
+  g1a pk;
+  const int dp = g1_decode_kc_pk(pk, pk48, kc);
+  return op_verify_l_rest<S, true>(dp, pk, msg, msg_len, sig96, F);
 }
 
 // tbls.Verify with the public key taken from the table (same statuses as op_verify); the Miller loop's f in LDS.
@@ -412,7 +466,8 @@ BLS_HD BLS_INLINE bool rlc_window(const f12l<LS>& F, uint64_t i0, uint64_t i1, c
 BLS_HD BLS_INLINE void rlc_items_lane(uint64_t i, const uint8_t* pks, const uint8_t* sigs, const uint32_t* msg_idx,
                                       uint64_t n, uint64_t n_msgs, const rlc_seed& seed, uint32_t* rpk,
                                       uint32_t* rsig, int32_t* status, const uint32_t* key_idx = nullptr,
-                                      uint64_t T = 0, const int32_t* tcode = nullptr, const uint32_t* tab = nullptr) {
+                                      uint64_t T = 0, const int32_t* tcode = nullptr, const uint32_t* tab = nullptr,
+                                      const keycache& kc = keycache{}) {
   uint32_t p[36], s[72];
   int st;
   if (msg_idx[i] >= n_msgs || (!pks && key_idx[i] >= T)) {  // device entry point: out-of-range index
@@ -424,7 +479,7 @@ BLS_HD BLS_INLINE void rlc_items_lane(uint64_t i, const uint8_t* pks, const uint
     for (int k = 0; k < 36; ++k) p[k] = (&ip.x.v[0])[k];
     for (int k = 0; k < 72; ++k) s[k] = (&is.x.c0.v[0])[k];
   } else if (pks) {
-    st = rlc_item(pks + 48 * i, sigs + 96 * i, seed, i, p, s);
+    st = rlc_item_kc(pks + 48 * i, sigs + 96 * i, seed, i, p, s, kc);  // kc off: the plain decode (g1_decode_kc_x)
   } else {
     g1a pk;
     g1j xpk;

@@ -27,19 +27,22 @@
 #define BLS_WIDE_ATTR
 #endif
 
+using bls::keycache;
 using bls::rlc_seed;
 constexpr int kWideBlock = 64;  // hipbls.hip kBlock
 
 // Stage 1: one lane per item -> status (final or RLC_PENDING), [r_i] pk_i and [r_i] sig_i in SoA.
-// pks == nullptr: public keys come from the resident pubshare table (key_idx, T, tcode, tab).
+// pks == nullptr: public keys come from the resident pubshare table (key_idx, T, tcode, tab); otherwise their decode
+// goes through the key cache kc (keycache.h; kc.entries == nullptr: off).
 extern "C" __global__ void __launch_bounds__(kWideBlock) BLS_WIDE_ATTR
 k_rlc_items(uint64_t i0, uint64_t i1, const uint8_t* __restrict__ pks, const uint8_t* __restrict__ sigs,
             const uint32_t* __restrict__ msg_idx, uint64_t n, uint64_t n_msgs, rlc_seed seed,
             uint32_t* __restrict__ rpk, uint32_t* __restrict__ rsig, int32_t* __restrict__ status,
             const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
-            const uint32_t* __restrict__ tab) {
+            const uint32_t* __restrict__ tab, keycache kc) {
   const uint64_t i = i0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (i < i1) bls::rlc_items_lane(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, rsig, status, key_idx, T, tcode, tab);
+  if (i < i1)
+    bls::rlc_items_lane(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, rsig, status, key_idx, T, tcode, tab, kc);
 }
 
 // Stage 2: one lane per message to hash -> H(m) in affine SoA (48 words) at its table column.  mlist lists the
@@ -59,9 +62,9 @@ k_rlcb_items(uint64_t n, const uint8_t* __restrict__ pks, const uint8_t* __restr
              uint32_t* __restrict__ pts, uint32_t* __restrict__ sc, int32_t* __restrict__ status,
              const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
              const uint32_t* __restrict__ tab, const uint32_t* __restrict__ g1pos, uint32_t* __restrict__ gpts,
-             uint32_t* __restrict__ gsc) {
+             uint32_t* __restrict__ gsc, keycache kc) {
   const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i < n)
     bls::rlcb_items_lane(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, pts, sc, status, key_idx, T, tcode, tab, g1pos,
-                         gpts, gsc);
+                         gpts, gsc, kc);
 }

@@ -70,7 +70,7 @@ BLS_HD BLS_INLINE void rlcb_items_lane(uint64_t i, const uint8_t* pks, const uin
                                        const uint32_t* key_idx = nullptr, uint64_t T = 0,
                                        const int32_t* tcode = nullptr, const uint32_t* tab = nullptr,
                                        const uint32_t* g1pos = nullptr, uint32_t* gpts = nullptr,
-                                       uint32_t* gsc = nullptr) {
+                                       uint32_t* gsc = nullptr, const keycache& kc = keycache{}) {
   g1j rp;
   jac_set_inf(rp);
   g2a sig, psig;
@@ -86,7 +86,7 @@ BLS_HD BLS_INLINE void rlcb_items_lane(uint64_t i, const uint8_t* pks, const uin
     const uint32_t slot = g1pos ? g1pos[i] : G1M_NONE;
     g1a pk;
     g1j xpk;
-    const int dp = pks ? g1_decompress_keep_x(pk, xpk, pks + 48 * i) : pubtab_get(pk, xpk, key_idx[i], T, tcode, tab);
+    const int dp = pks ? g1_decode_kc_x(pk, xpk, pks + 48 * i, kc) : pubtab_get(pk, xpk, key_idx[i], T, tcode, tab);
     st = RLC_PENDING;
     if (dp == DEC_BAD) st = HIPBLS_ERR_PUBKEY;
     if (st == RLC_PENDING) {

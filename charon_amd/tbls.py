@@ -91,6 +91,8 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_aggregate_device": ([vp, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_hcache_config": ([u64], ctypes.c_int),
         "hipbls_hcache_stats": ([u64p, u64p, u64p], ctypes.c_int),
+        "hipbls_keycache_config": ([u64], ctypes.c_int),
+        "hipbls_keycache_stats": ([u64p, u64p, u64p], ctypes.c_int),
         "hipbls_abi_version": ([], ctypes.c_int),
         "hipbls_init": ([ctypes.c_int], ctypes.c_int),
         "hipbls_device_count": ([], ctypes.c_int),
@@ -157,6 +159,7 @@ def exported_symbols() -> List[str]:
         "hipbls_rlc_set_g1_msm_min", "hipbls_scratch_budget", "hipbls_stream_joins", "hipbls_kernel_names",
         "hipbls_queue_worker_stats", "hipbls_set_latency_replicas", "hipbls_build_id",
         "hipbls_threshold_aggregate_verify_batch_keys", "hipbls_threshold_aggregate_verify_batch_keys_device",
+        "hipbls_keycache_config", "hipbls_keycache_stats",
     ]
 
 
@@ -657,6 +660,17 @@ class HipBLS:
     def hcache_stats(self) -> Tuple[int, int, int]:
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self.lib.hipbls_hcache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), self.lib)
+        return a.value, b.value, c.value
+
+    # ---------------------------------------------------------------- resident key cache (wire-format calls)
+    def keycache_config(self, slots: int) -> None:
+        """Empty the key cache and size it to `slots` (rounded up to a power of two; 0 = off)."""
+        _check(self.lib.hipbls_keycache_config(slots), self.lib)
+
+    def keycache_stats(self) -> Tuple[int, int, int]:
+        """(hits, misses, inserts) since the last keycache_config, summed over contexts."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self.lib.hipbls_keycache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), self.lib)
         return a.value, b.value, c.value
 
     # ---------------------------------------------------------------- pairing-check layout

@@ -268,6 +268,19 @@ int hipbls_rlc_batch_stats(uint64_t* attempted, uint64_t* passed, int32_t* last)
 int hipbls_hcache_config(uint64_t capacity);
 int hipbls_hcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries);
 
+/* Resident key cache used by the wire-format calls (hipbls_verify_batch[_device], hipbls_batch_verify_rlc[_device],
+ * the submission queue's wire batches): the kernels look each 48-byte public key up in a per-context table in HBM and,
+ * on a hit, skip its decompression and subgroup test; a key that decodes as a valid G1 point is published once and
+ * never replaced (no eviction: a full probe window means the key is not cached).  Invalid encodings, points outside G1
+ * and the infinity key are never cached.  Statuses are unchanged by the cache.  `slots` is rounded up to a power of
+ * two (256 B each); 0 turns the cache off.  Default: 65,536 slots per context, or HIPBLS_KEYCACHE_SLOTS.  The call
+ * waits for the device and empties the cache and its counters; it may run beside any other call, hipbls_verify
+ * included (no kernel is enqueued on buffers it has released).  Stats are summed over contexts: items served from the
+ * cache, items decoded by the kernel, entries written.  hipbls_keycache_stats also waits for the device, with each
+ * context's lock held, so that it counts every call enqueued before it: a diagnostic, not for a hot path. */
+int hipbls_keycache_config(uint64_t slots);
+int hipbls_keycache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts);
+
 /* ------------------------------------------- device-resident variants (inputs already in HBM) ---- */
 /* Same semantics; every pointer is a device pointer; work is enqueued on `stream` (a hipStream_t,
  * NULL = the library's own non-blocking stream of that device, which is NOT ordered with the caller's default
