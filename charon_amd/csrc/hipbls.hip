@@ -42,6 +42,7 @@
 
 #include <sys/random.h>
 
+#include "hcache_assign.h"
 #include "kernels.h"
 #include "ranges.h"
 
@@ -84,6 +85,9 @@ __global__ void k_tv_prep8_keys(const uint32_t* key_idx, uint64_t T, const int32
                                 uint64_t n_msgs, uint32_t* Hc, uint64_t G, const int64_t* ids, const uint64_t* goffs,
                                 uint32_t* ws, int32_t* vstatus, const uint8_t* sigs, uint64_t n_parts, uint32_t* pts,
                                 int32_t* pstat);
+__global__ void k_verify_prep8_keys(const uint8_t* msgs, const uint64_t* moffs, const uint32_t* mlist, uint64_t n_hash,
+                                    const uint32_t* hslot, uint32_t* H, uint64_t hstride, const uint8_t* sigs,
+                                    uint64_t n, uint32_t* ws);
 }  // namespace bls_fp2p
 // The sixteen-lane check for batches of at most four items (verify_hex.hip: BLS_FP2_PAIR + BLS_HEX, namespace bls_hex).
 namespace bls_hex {
@@ -142,14 +146,9 @@ struct TimingSlot {
 // different calls (one parsigex message per peer, core/parsigex/parsigex.go:86-91, then sigagg,
 // core/sigagg/sigagg.go:138-159), so each distinct root is hashed to G2 once and kept in HBM (affine, 48 words,
 // SoA over the capacity).  FIFO replacement over a ring of slots; a hit whose slot this call is about to reuse
-// is treated as a miss.
-struct HCache {
-  uint64_t cap = 0;  // 0 = disabled
-  uint64_t ring = 0;
-  std::unordered_map<std::string, uint32_t> map;
-  std::vector<std::string> key_of;  // slot -> key ("" = empty)
+// is treated as a miss.  The bookkeeping (map, ring, counters, hcache_assign) is hcache_assign.h's.
+struct HCache : HCacheState {
   DevBuf table;
-  uint64_t hits = 0, misses = 0;
 };
 
 // Resident key cache (keycache.h): wire bytes of a public key -> its decoded form, filled and
@@ -225,6 +224,7 @@ struct VerifyQueue {
   QSlot slot[kSlots];
   std::deque<int> inflight;  // slots in launch order
   DevBuf d_pk, d_sig, d_msg, d_off, d_kidx, d_midx, d_slot, d_mlist, d_rlc_st;
+  DevBuf d_vk_h, d_vk_ws;  // small keyed batches (verify_keys_lat): the batch's own H(m) table, prep + check workspace
   // host staging of the keyed path (reused across batches)
   std::vector<uint32_t> kidx, midx, order, slotv, miss;
   std::vector<uint8_t> sig_sorted, umsg;
@@ -242,6 +242,9 @@ struct Context {
   DevBuf t_code, t_tab, b_kidx;                                            // resident pubshare table + key indices
   DevBuf f_ws;  // FastAggregateVerify on the octet / sixteen-lane layouts: per-group H(m), signature, codes
   DevBuf v_ws;                                                             // lane-pair Verify points (SoA)
+  // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
+  // the call's own H(m) table and its prep + check workspace; used under the lock up to the call's stream sync
+  DevBuf vk_midx, vk_slot, vk_mlist, vk_h, vk_ws;
   // sigagg in one call (launch_tagg_verify): two workspace sets used alternately, each with the completion event of
   // the call that last used it
   DevBuf tv_pts[2], tv_pst[2], tv_ws[2], tv_aux[2];
@@ -457,6 +460,7 @@ const KernelRef kKernels[] = {
     KREF16(k_verify_pair_lq16), KREF8(k_fav_prep8), KREF16W(k_fav_pair_lq16),
     KREF8(k_tv_prep8), KREF8(k_tagg_sum8), KREF16(k_tv_pair_lq16),
     KREF(k_tv_phase_a_keys), KREF(k_tv_join_keys), KREF(k_tv_gather_keys), KREF8(k_tv_prep8_keys),
+    KREF(k_verify_gather_keys), KREF8(k_verify_prep8_keys),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -1014,6 +1018,55 @@ bool use_octets(uint64_t n) {
   return mode == HIPBLS_PAIR_AUTO && n <= kLq8MaxVerify;
 }
 
+// The prep + check workspace of n items: 120 words per item,
+// + two decode codes per item for the octet path, and the octet path's race words in the buffer's last 64 bytes (a
+// fixed place per allocation, 64-byte aligned since the capacity is a multiple of 256, beyond every batch's data;
+// zeroed when the buffer is allocated, then only ever written with a launch's epoch, so a stale word never equals a
+// new epoch)
+int verify_ws_ensure(DevBuf& ws, uint64_t n, hipStream_t s) {
+  void* const before = ws.p;
+  HIP_TRY(ws.ensure(n * 122 * 4 + 128));
+  if (ws.p != before) HIP_TRY(hipMemsetAsync((uint8_t*)ws.p + ws.cap - 64, 0, 64, s));
+  return HIPBLS_OK;
+}
+
+// A batch of one workgroup (<= 8 items: the drop-in n = 1 calls) races `lat_replicas` copies of it, one per XCD
+// (verify_lat.hip bls_race): the first copy to finish each stage wins.  Race words after the workspace.
+struct OctRace {
+  unsigned g8;
+  uint32_t* race;
+  uint32_t reps, epoch;
+};
+OctRace oct_race(const DevBuf& ws, uint64_t n) {
+  OctRace R;
+  R.g8 = (unsigned)((8 * n + 63) / 64);
+  R.race = (uint32_t*)((uint8_t*)ws.p + ws.cap - 64);
+  // (the race words must be naturally aligned: a misaligned word faults the device -- round 5, before capacities
+  // were rounded to 256 bytes)
+  R.reps = R.g8 == 1 && ((uintptr_t)R.race & 63) == 0 ? g_lat_replicas.load() : 1u;
+  R.epoch = R.reps > 1 ? g_race_epoch.fetch_add(1) + 1u : 0u;
+  if (R.reps > 1 && R.epoch == 0) R.epoch = g_race_epoch.fetch_add(1) + 1u;  // 0 is a fresh word's value
+  return R;
+}
+
+// The octet path's check stage over a prepared workspace (k_verify_prep8's contract), for launch_verify and the keyed
+// latency route (verify_keys_lat): sixteen lanes per item up to four items, eight above.
+int launch_oct_check(Context& c, const DevBuf& ws, uint64_t n, int32_t* d_status, hipStream_t s, const OctRace& R) {
+  return timed(c, use_hex(n) ? "verify_pair_lq16" : "verify_pair_lq8", s, [&] {
+#if defined(BLS_LQ8_XCD_PROBE) && BLS_LQ8_XCD_PROBE
+    hipLaunchKernelGGL(bls_fp2p::k_verify_pair_lq8, dim3(8 * R.g8), dim3(kBlock), 0, s, (const uint32_t*)ws.p, n,
+                       d_status, 1u, R.race, 0u);  // experiment build: every workgroup once per XCD (verify_lat.hip)
+#else
+    if (use_hex(n))  // n <= 4: one workgroup of sixteen lanes per item, like g8 == 1
+      hipLaunchKernelGGL(bls_hex::k_verify_pair_lq16, dim3(R.g8 * R.reps), dim3(kBlock), 0, s, (const uint32_t*)ws.p,
+                         n, d_status, R.reps, R.race, R.epoch);
+    else
+      hipLaunchKernelGGL(bls_fp2p::k_verify_pair_lq8, dim3(R.g8 * R.reps), dim3(kBlock), 0, s, (const uint32_t*)ws.p,
+                         n, d_status, R.reps, R.race, R.epoch);
+#endif
+  });
+}
+
 // Verify: fused (one lane per item) or prep + lane-pair check; `ws` is the caller's SoA workspace for the latter
 // (120 words per item), so the library stream and the queue worker never share one.
 int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_offs,
@@ -1025,43 +1078,18 @@ int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const
       hipLaunchKernelGGL(k_verify_fused, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs,
                          d_sigs, n, d_status, c.kcache.dev());
     });
-  // + two decode codes per item for the octet path, and the octet path's race words in the buffer's last 64 bytes (a
-  // fixed place per allocation, 64-byte aligned since the capacity is a multiple of 256, beyond every batch's data;
-  // zeroed when the buffer is allocated, then only ever written with a launch's epoch, so a stale word never equals a
-  // new epoch)
-  void* const before = ws.p;
-  HIP_TRY(ws.ensure(n * 122 * 4 + 128));
-  if (ws.p != before) HIP_TRY(hipMemsetAsync((uint8_t*)ws.p + ws.cap - 64, 0, 64, s));
+  int rc = verify_ws_ensure(ws, n, s);
+  if (rc) return rc;
   if (use_octets(n)) {
-    const unsigned g8 = (unsigned)grid_for(8 * n);
-    // A batch of one workgroup (<= 8 items: the drop-in n = 1 calls) races `lat_replicas` copies of it, one per XCD
-    // (verify_lat.hip bls_race): the first copy to finish each stage wins.  Race words after the workspace.
-    uint32_t* race = (uint32_t*)((uint8_t*)ws.p + ws.cap - 64);
-    // (the race words must be naturally aligned: a misaligned word faults the device -- round 5, before capacities
-    // were rounded to 256 bytes)
-    const uint32_t reps = g8 == 1 && ((uintptr_t)race & 63) == 0 ? g_lat_replicas.load() : 1u;
-    uint32_t epoch = reps > 1 ? g_race_epoch.fetch_add(1) + 1u : 0u;
-    if (reps > 1 && epoch == 0) epoch = g_race_epoch.fetch_add(1) + 1u;  // 0 is a fresh word's value
-    int rc = timed(c, "verify_prep8", s, [&] {  // three roles: key, signature, hash (verify_lat.hip)
-      hipLaunchKernelGGL(bls_fp2p::k_verify_prep8, dim3(3 * g8 * reps), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs,
-                         d_sigs, n, (uint32_t*)ws.p, d_status, reps, race, epoch);
+    const OctRace R = oct_race(ws, n);
+    rc = timed(c, "verify_prep8", s, [&] {  // three roles: key, signature, hash (verify_lat.hip)
+      hipLaunchKernelGGL(bls_fp2p::k_verify_prep8, dim3(3 * R.g8 * R.reps), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs,
+                         d_sigs, n, (uint32_t*)ws.p, d_status, R.reps, R.race, R.epoch);
     });
     if (rc) return rc;
-    return timed(c, use_hex(n) ? "verify_pair_lq16" : "verify_pair_lq8", s, [&] {
-#if defined(BLS_LQ8_XCD_PROBE) && BLS_LQ8_XCD_PROBE
-      hipLaunchKernelGGL(bls_fp2p::k_verify_pair_lq8, dim3(8 * g8), dim3(kBlock), 0, s, (const uint32_t*)ws.p, n,
-                         d_status, 1u, race, 0u);  // experiment build: every workgroup once per XCD (verify_lat.hip)
-#else
-      if (use_hex(n))  // n <= 4: one workgroup of sixteen lanes per item, like g8 == 1
-        hipLaunchKernelGGL(bls_hex::k_verify_pair_lq16, dim3(g8 * reps), dim3(kBlock), 0, s, (const uint32_t*)ws.p, n,
-                           d_status, reps, race, epoch);
-      else
-        hipLaunchKernelGGL(bls_fp2p::k_verify_pair_lq8, dim3(g8 * reps), dim3(kBlock), 0, s, (const uint32_t*)ws.p, n,
-                           d_status, reps, race, epoch);
-#endif
-    });
+    return launch_oct_check(c, ws, n, d_status, s, R);
   }
-  int rc = timed(c, "verify_prep", s, [&] {
+  rc = timed(c, "verify_prep", s, [&] {
     const int pair_hash = n <= kPairHashMaxVerify ? 1 : 0;
     KC_LAUNCH_GUARD(c);
     hipLaunchKernelGGL(k_verify_prep, dim3((unsigned)((pair_hash ? 3 : 2) * grid_for(n))), dim3(kBlock), 0, s, d_pks,
@@ -1901,53 +1929,7 @@ bool groups_ok(const uint64_t* goffs, uint64_t n_groups) {
 }
 
 // ============================================================================ H(m) cache
-// Assigns cache columns for the n_msgs distinct messages of one call: fills slot[m] and the list of messages that
-// must be hashed (misses).  Returns false (cache bypassed) when disabled or the call has more messages than slots.
-bool hcache_assign(HCache& hc, const uint8_t* msgs, const uint64_t* offs, uint64_t n_msgs, std::vector<uint32_t>& slot,
-                   std::vector<uint32_t>& miss) {
-  if (hc.cap == 0 || n_msgs > hc.cap) return false;
-  slot.assign(n_msgs, 0);
-  miss.clear();
-  std::vector<std::string> keys(n_msgs);
-  std::vector<char> hit(n_msgs, 0);
-  for (uint64_t m = 0; m < n_msgs; ++m) {
-    keys[m].assign((const char*)msgs + offs[m], offs[m + 1] - offs[m]);
-    auto it = hc.map.find(keys[m]);
-    if (it != hc.map.end()) {
-      slot[m] = (uint32_t)it->second;
-      hit[m] = 1;
-    }
-  }
-  // The misses take slots [ring, ring + k); a hit inside that range would be overwritten by this very call, so it
-  // is demoted to a miss (which grows k): iterate to the fixed point.
-  for (;;) {
-    uint64_t k = 0;
-    for (uint64_t m = 0; m < n_msgs; ++m) k += hit[m] ? 0 : 1;
-    bool changed = false;
-    for (uint64_t m = 0; m < n_msgs; ++m)
-      if (hit[m] && (slot[m] + hc.cap - hc.ring) % hc.cap < k) {
-        hit[m] = 0;
-        changed = true;
-      }
-    if (!changed) break;
-  }
-  for (uint64_t m = 0; m < n_msgs; ++m) {
-    if (hit[m]) {
-      hc.hits += 1;
-      continue;
-    }
-    // messages are distinct within a call (the caller's message table), so each miss takes its own slot
-    const uint32_t s = (uint32_t)hc.ring;
-    hc.ring = (hc.ring + 1) % hc.cap;
-    if (!hc.key_of[s].empty()) hc.map.erase(hc.key_of[s]);
-    hc.key_of[s] = keys[m];
-    hc.map[keys[m]] = s;
-    slot[m] = s;
-    miss.push_back((uint32_t)m);
-    hc.misses += 1;
-  }
-  return true;
-}
+// hcache_assign / hcache_erase_misses: hcache_assign.h (host-only, also built by tests/test_verify_keys_lat_static.py).
 
 // Host-buffer RLC body shared by the wire-format and key-table calls, on one context (lock held), stream `s` with
 // the given workspaces for the inputs.  The H(m) table is the context's cache when enabled, else per call.
@@ -2057,6 +2039,122 @@ int rlc_range(Context& c, const uint8_t* pks, const uint32_t* key_idx, const uin
                   lmsg.data(), loff.data(), used.size(), seed, status + lo, call);
 }
 
+// ============================================================================ keyed Verify, latency route
+// tbls.Verify by resident key index on the drop-in path's layouts, for hipbls_verify_batch_keys and
+// the submission queue's keyed batches below kQueueKeyedMin items: the signatures and the missing H(m) on octets
+// (verify_lat.hip k_verify_prep8_keys), the keys, their codes and each item's H(m) copied in from the table and the
+// cache (kernels.h k_verify_gather_keys), then launch_verify's own check stage.  H(m) goes through the context's H(m)
+// cache (a miss inserts: this call is a producer), or into the call's own table when the cache is off or smaller than
+// the call.  HIPBLS_LAT_VERIFY_KEYS=0 keeps k_verify_keys and, in the queue, run_batch_keyed.
+bool initial_lat_verify_keys() {
+  const char* e = getenv("HIPBLS_LAT_VERIFY_KEYS");
+  return !(e && e[0] == '0');
+}
+const bool g_lat_verify_keys = initial_lat_verify_keys();
+bool use_verify_keys_lat(uint64_t n) { return g_lat_verify_keys && use_octets(n); }
+
+// The distinct messages of n items in first-use order (umsg / uoff) and each item's index among them.
+void distinct_messages(const uint8_t* msgs, const uint64_t* offs, uint64_t n, std::vector<uint8_t>& umsg,
+                       std::vector<uint64_t>& uoff, std::vector<uint32_t>& mid) {
+  std::unordered_map<std::string, uint32_t> pos;
+  mid.resize(n);
+  umsg.clear();
+  uoff.assign(1, 0);
+  for (uint64_t i = 0; i < n; ++i) {
+    std::string key((const char*)msgs + offs[i], offs[i + 1] - offs[i]);
+    auto it = pos.find(key);
+    if (it == pos.end()) {
+      it = pos.emplace(std::move(key), (uint32_t)(uoff.size() - 1)).first;
+      umsg.insert(umsg.end(), msgs + offs[i], msgs + offs[i + 1]);
+      uoff.push_back(umsg.size());
+    }
+    mid[i] = it->second;
+  }
+}
+
+// One context (lock held), stream `s`, the caller's buffers; returns after the stream has drained, so a column found
+// in the cache's map has been written and every read of a column here is over before the lock is released.
+struct VkBufs {
+  DevBuf *kidx, *sig, *msg, *off, *midx, *slot, *mlist, *h, *ws, *st;
+};
+int verify_keys_lat(Context& c, VkBufs B, hipStream_t s, const uint32_t* key_idx, const uint8_t* sigs,
+                    const uint32_t* mid, uint64_t n, const uint8_t* umsg, const uint64_t* uoff, uint64_t n_msgs,
+                    int32_t* status) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (key_idx[i] >= c.t_size) return arg_err("key index outside the pubshare table");
+  const uint64_t msg_total = uoff[n_msgs];
+  std::vector<uint32_t> slot, miss;
+  const bool cached = hcache_assign(c.hcache, umsg, uoff, n_msgs, slot, miss);
+  // Every exit but the last drains the stream (no queued copy reads a freed host vector) and takes this call's misses
+  // out of the map again: their columns may never have been written.
+  struct Undo {
+    Context& c;
+    hipStream_t s;
+    const uint8_t* umsg;
+    const uint64_t* uoff;
+    const std::vector<uint32_t>&slot, &miss;
+    bool cached, on = true;
+    ~Undo() {
+      if (!on) return;
+      (void)hipStreamSynchronize(s);
+      if (cached) hcache_erase_misses(c.hcache, umsg, uoff, slot, miss);
+    }
+  } undo{c, s, umsg, uoff, slot, miss, cached};
+  HIP_TRY(B.kidx->ensure(n * 4));
+  HIP_TRY(B.sig->ensure(n * 96));
+  HIP_TRY(B.msg->ensure(msg_total ? msg_total : 1));
+  HIP_TRY(B.off->ensure((n_msgs + 1) * 8));
+  HIP_TRY(B.midx->ensure(n * 4));
+  HIP_TRY(B.st->ensure(n * 4));
+  int rc = verify_ws_ensure(*B.ws, n, s);
+  if (rc) return rc;
+  uint32_t* dH = nullptr;
+  const uint32_t *dslot = nullptr, *dmiss = nullptr;
+  uint64_t stride = n_msgs, n_hash = n_msgs;
+  if (cached) {
+    HIP_TRY(B.slot->ensure(n_msgs * 4));
+    HIP_TRY(B.mlist->ensure((miss.size() ? miss.size() : 1) * 4));
+    // a keyed sigagg call that released the lock may still be gathering H(m) from columns the misses are about to take
+    if (c.tv_hread && miss.size()) HIP_TRY(hipStreamWaitEvent(s, c.tv_hread, 0));
+    HIP_TRY(hipMemcpyAsync(B.slot->p, slot.data(), n_msgs * 4, hipMemcpyHostToDevice, s));
+    if (miss.size()) HIP_TRY(hipMemcpyAsync(B.mlist->p, miss.data(), miss.size() * 4, hipMemcpyHostToDevice, s));
+    dH = (uint32_t*)c.hcache.table.p;
+    stride = c.hcache.cap;
+    dslot = (const uint32_t*)B.slot->p;
+    dmiss = (const uint32_t*)B.mlist->p;
+    n_hash = miss.size();
+  } else {
+    HIP_TRY(B.h->ensure(n_msgs * 48 * 4));
+    dH = (uint32_t*)B.h->p;
+  }
+  HIP_TRY(hipMemcpyAsync(B.kidx->p, key_idx, n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(B.sig->p, sigs, n * 96, hipMemcpyHostToDevice, s));
+  if (msg_total) HIP_TRY(hipMemcpyAsync(B.msg->p, umsg, msg_total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(B.off->p, uoff, (n_msgs + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(B.midx->p, mid, n * 4, hipMemcpyHostToDevice, s));
+  uint32_t* ws = (uint32_t*)B.ws->p;
+  const OctRace R = oct_race(*B.ws, n);  // the check's race; the prep is not raced
+  const uint64_t nbh = (8 * n_hash + kBlock - 1) / kBlock, nbs = (8 * n + kBlock - 1) / kBlock;
+  rc = timed(c, "verify_prep8_keys", s, [&] {
+    hipLaunchKernelGGL(bls_fp2p::k_verify_prep8_keys, dim3((unsigned)(nbh + nbs)), dim3(kBlock), 0, s,
+                       (const uint8_t*)B.msg->p, (const uint64_t*)B.off->p, dmiss, n_hash, dslot, dH, stride,
+                       (const uint8_t*)B.sig->p, n, ws);
+  });
+  if (rc) return rc;
+  rc = timed(c, "verify_gather_keys", s, [&] {
+    hipLaunchKernelGGL(k_verify_gather_keys, dim3((unsigned)grid_for(72 * n)), dim3(kBlock), 0, s, n,
+                       (const uint32_t*)B.kidx->p, c.t_size, (const int32_t*)c.t_code.p, (const uint32_t*)c.t_tab.p,
+                       (const uint32_t*)B.midx->p, dslot, (const uint32_t*)dH, stride, ws);
+  });
+  if (rc) return rc;
+  rc = launch_oct_check(c, *B.ws, n, (int32_t*)B.st->p, s, R);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(status, B.st->p, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  undo.on = false;
+  return HIPBLS_OK;
+}
+
 // ============================================================================ submission queue
 // Coalesces concurrent single-item Verify calls (tbls.Verify from parsigex / validatorapi / sigagg goroutines,
 // core/parsigex/parsigex.go:86-91, core/validatorapi/validatorapi.go:246-283) into batched launches.  Each context
@@ -2071,7 +2169,9 @@ int rlc_range(Context& c, const uint8_t* pks, const uint32_t* key_idx, const uin
 // RLC BatchVerify with keys by table index (no decode or subgroup test per call, herumi.go:286-289 does both every
 // time) over the batch's DISTINCT messages, through the context's H(m) cache: a root shared by a validator's t
 // partials or by a committee is hashed once, and once across batches while it stays cached.  Statuses are exactly
-// the per-item Verify's (rlc.h).  Batches with a key outside the table take the wire-format Verify.
+// the per-item Verify's (rlc.h).  Batches with a key outside the table take the wire-format Verify.  A keyed batch
+// below kQueueKeyedMin items (only with the cache enabled) is not worth an RLC check on single lanes: it takes the
+// keyed Verify latency route (verify_keys_lat: octets / sixteen lanes, same table, same cache, a miss inserts).
 std::atomic<uint64_t> g_q_max_batch{65536};
 // 50 us: what an idle worker waits for company before launching a small batch; callers arriving while a batch runs
 // coalesce into the next one regardless (two batches in flight).  Serial callers (the parsigex loop: a running mean
@@ -2119,21 +2219,8 @@ int wire_finish(QSlot& k) {
 int run_batch_keyed(Context& c, VBatch& b) {
   VerifyQueue& q = c.q;
   const uint64_t n = b.n();
-  // distinct messages in first-use order
-  std::unordered_map<std::string, uint32_t> pos;
-  std::vector<uint32_t> mid(n);
-  q.umsg.clear();
-  q.uoff.assign(1, 0);
-  for (uint64_t i = 0; i < n; ++i) {
-    std::string key((const char*)b.msg.data() + b.off[i], b.off[i + 1] - b.off[i]);
-    auto it = pos.find(key);
-    if (it == pos.end()) {
-      it = pos.emplace(std::move(key), (uint32_t)(q.uoff.size() - 1)).first;
-      q.umsg.insert(q.umsg.end(), b.msg.begin() + b.off[i], b.msg.begin() + b.off[i + 1]);
-      q.uoff.push_back(q.umsg.size());
-    }
-    mid[i] = it->second;
-  }
+  std::vector<uint32_t> mid;
+  distinct_messages(b.msg.data(), b.off.data(), n, q.umsg, q.uoff, mid);
   const uint64_t n_msgs = q.uoff.size() - 1;
   // counting sort by message
   std::vector<uint64_t> start(n_msgs + 1, 0);
@@ -2163,11 +2250,25 @@ int run_batch_keyed(Context& c, VBatch& b) {
   return HIPBLS_OK;
 }
 
+// A keyed batch below kQueueKeyedMin items (a lone tbls.Verify of a serial caller): the keyed Verify latency route on
+// the queue's own stream and buffers, under the context lock like run_batch_keyed; per-item statuses, no reordering.
+int run_batch_keyed_lat(Context& c, VBatch& b) {
+  VerifyQueue& q = c.q;
+  const uint64_t n = b.n();
+  distinct_messages(b.msg.data(), b.off.data(), n, q.umsg, q.uoff, q.midx);
+  q.kidx.resize(n);
+  for (uint64_t i = 0; i < n; ++i) q.kidx[i] = c.t_index.at(std::string((const char*)b.pk.data() + 48 * i, 48));
+  VkBufs B{&q.d_kidx, &q.d_sig, &q.d_msg, &q.d_off, &q.d_midx, &q.d_slot, &q.d_mlist, &q.d_vk_h, &q.d_vk_ws, &q.d_rlc_st};
+  return verify_keys_lat(c, B, q.stream, q.kidx.data(), b.sig.data(), q.midx.data(), n, q.umsg.data(), q.uoff.data(),
+                         q.uoff.size() - 1, b.status.data());
+}
+
 // The keyed path when every key of the batch is in the table (run here, synchronously); otherwise false.
 bool try_keyed(Context& c, VBatch& b, int& rc) {
   const uint64_t n = b.n();
   std::lock_guard<std::mutex> lk(c.mu);
-  // small batches take the lower-latency lane-pair Verify, unless the caller enabled the H(m) cache
+  // small batches take the lower-latency lane-pair Verify, unless the caller enabled the H(m) cache: then they run
+  // keyed too, on the keyed Verify latency route (run_batch_keyed_lat) rather than as an RLC batch of a few items
   bool keyed = c.t_size > 0 && (n >= kQueueKeyedMin || c.hcache.cap > 0);
   uint64_t miss_at = n;
   for (uint64_t i = 0; keyed && i < n; ++i) {
@@ -2181,7 +2282,7 @@ bool try_keyed(Context& c, VBatch& b, int& rc) {
             (unsigned long long)miss_at);
   if (!keyed) return false;
   c.q.keyed += 1;
-  rc = run_batch_keyed(c, b);
+  rc = n < kQueueKeyedMin && use_verify_keys_lat(n) ? run_batch_keyed_lat(c, b) : run_batch_keyed(c, b);
   return true;
 }
 
@@ -2639,6 +2740,15 @@ int aggregate_host(Context& c, const uint8_t* sigs, uint64_t n, uint8_t* out_sig
 
 int verify_keys_host(Context& c, const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* offs,
                      const uint8_t* sigs, uint64_t n, int32_t* status) {
+  if (use_verify_keys_lat(n)) {  // the latency route: octets / sixteen lanes, H(m) through the cache
+    std::vector<uint8_t> umsg;
+    std::vector<uint64_t> uoff;
+    std::vector<uint32_t> mid;
+    distinct_messages(msgs, offs, n, umsg, uoff, mid);
+    VkBufs B{&c.b_kidx, &c.b_sig, &c.b_msg, &c.b_off, &c.vk_midx, &c.vk_slot, &c.vk_mlist, &c.vk_h, &c.vk_ws, &c.b_st};
+    return verify_keys_lat(c, B, c.stream, key_idx, sigs, mid.data(), n, umsg.data(), uoff.data(), uoff.size() - 1,
+                           status);
+  }
   const uint64_t msg_total = offs[n];
   HIP_TRY(c.b_kidx.ensure(n * 4));
   HIP_TRY(c.b_sig.ensure(n * 96));
@@ -3399,11 +3509,7 @@ int hipbls_hcache_config(uint64_t capacity) {
   return run_all([&](Context& c) -> int {
     HCache& hc = c.hcache;
     HIP_TRY(hipDeviceSynchronize());  // no call may still read the old table
-    hc.map.clear();
-    hc.key_of.assign(capacity, std::string());
-    hc.ring = 0;
-    hc.hits = hc.misses = 0;
-    hc.cap = capacity;
+    hcache_reset(hc, capacity);
     if (capacity) HIP_TRY(hc.table.ensure(capacity * 48 * 4));
     return HIPBLS_OK;
   });

@@ -567,6 +567,31 @@ __global__ void __launch_bounds__(kBlock) k_tv_gather_keys(uint64_t n, const uin
   if (!after) ws[(uint64_t)(24 + w) * n + i] = tv_h_word(m, w, hsrc, Hcache, cstride, Hc, n_msgs);
 }
 
+// The keyed Verify latency route's gather (between verify_lat.hip k_verify_prep8_keys and the octet / sixteen-lane
+// check, whose workspace it completes), one lane per word, 72 words per item: the table's affine key (pubtab_get's
+// first 24 words) to ws, H(message of item i) from column hslot[msg_idx[i]] of H (stride hstride: the H(m) cache, or
+// without hslot column msg_idx[i] of the call's own table) to ws + 24 n, and the table's DEC_* code to codes[2 i].
+// The host refuses an index outside the table up front; here it only keeps the loads in bounds.
+__global__ void __launch_bounds__(kBlock) k_verify_gather_keys(uint64_t n, const uint32_t* __restrict__ key_idx,
+                                                               uint64_t T, const int32_t* __restrict__ tcode,
+                                                               const uint32_t* __restrict__ tab,
+                                                               const uint32_t* __restrict__ msg_idx,
+                                                               const uint32_t* __restrict__ hslot,
+                                                               const uint32_t* __restrict__ H, uint64_t hstride,
+                                                               uint32_t* __restrict__ ws) {
+  const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t i = t / 72;
+  const int w = (int)(t % 72);
+  if (i >= n) return;
+  const uint64_t k = key_idx[i];
+  if (w >= 24) {
+    ws[(uint64_t)w * n + i] = H[(uint64_t)(w - 24) * hstride + h_col(hslot, msg_idx[i])];
+    return;
+  }
+  if (w == 0) ((int32_t*)(ws + 120 * n))[2 * i] = k < T ? tcode[k] : DEC_BAD;
+  if (k < T) ws[(uint64_t)w * n + i] = tab[(uint64_t)w * T + k];
+}
+
 // sigagg's pairing check on lane quads beside [L^-1] S (roles per workgroup, uniform): workgroups [0, grid_for(4 n))
 // run k_verify_pair_lq4's lanes, the rest k_tagg_unscale's.  Both only read ws.
 __global__ void __launch_bounds__(kBlock) k_tv_check_unscale(const uint32_t* __restrict__ ws, uint64_t n,

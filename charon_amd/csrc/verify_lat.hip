@@ -126,6 +126,45 @@ __global__ void __launch_bounds__(kOctBlock) k_verify_prep8(const uint8_t* __res
   bls_race::finish();
 }
 
+// k_verify_prep8 for the call with keys by table index (hipbls_verify_batch_keys and the submission queue's small
+// keyed batches; hipbls.hip verify_keys_lat), same workspace: two roles, uniform per workgroup, the hash blocks first
+// (the longer role).  The hash blocks take one octet per message of the miss list (mlist, or 0 .. n_hash - 1 without
+// one; moffs are the DISTINCT messages' offsets) and write H(m) into column hslot[m] of H (stride hstride): the
+// context's H(m) cache, or without hslot column m of the call's own table.  The signature blocks are k_verify_prep8's
+// role 1.  ws gets the signatures and their codes only: kernels.h k_verify_gather_keys copies each item's key, key
+// code and H(m) in behind this kernel.  Not raced: replicas would all store into a shared cache column.
+__global__ void __launch_bounds__(kOctBlock) k_verify_prep8_keys(
+    const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ moffs, const uint32_t* __restrict__ mlist,
+    uint64_t n_hash, const uint32_t* __restrict__ hslot, uint32_t* __restrict__ H, uint64_t hstride,
+    const uint8_t* __restrict__ sigs, uint64_t n, uint32_t* __restrict__ ws) {
+  bls_race::init(nullptr, 0u);
+  const uint64_t nbh = (8 * n_hash + kOctBlock - 1) / kOctBlock;
+  const bool hash = blockIdx.x < nbh;  // uniform per workgroup
+  const uint64_t t = (blockIdx.x - (hash ? 0 : nbh)) * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t i = t >> 3;
+  const bool lead = (t & 7) == 0;
+  if (hash) {
+    if (i >= n_hash) return;  // the same on all eight lanes
+    const uint32_t m = (t & 1) ? ~0u : 0u;
+    const uint64_t msg = mlist ? mlist[i] : i;
+    const uint64_t o0 = moffs[msg], o1 = moffs[msg + 1];
+    g2j sum, hj;
+    hash_to_g2_pair_sum(sum, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, m);
+    g2_clear_cofactor_quad(hj, sum, (int)(t & 3));
+    g2a hm;
+    jac_to_aff(hm, hj);
+    if (lead) soa_store<48>(H, hstride, h_col(hslot, msg), &hm.x.c0.v[0]);
+    return;
+  }
+  if (i >= n) return;
+  g2a sig;
+  const int ds = g2_decompress(sig, sigs + 96 * i, false);  // G2 membership: from the signature's Miller loop
+  if (lead) {
+    ((int32_t*)(ws + 120 * n))[2 * i + 1] = ds;
+    if (ds == DEC_OK) soa_store<48>(ws + 72 * n, n, i, &sig.x.c0.v[0]);
+  }
+}
+
 // FastAggregateVerify's stage 1 for a few groups (tbls/herumi.go:315-339; hipbls.hip launch_fav, the sync committee's
 // one aggregate per slot), eight lanes per unit: every key of every group decoded + subgroup-tested (pts: affine SoA
 // with stride nkeys, kcode: DEC_* per key), beside each group's signature decode and message hash exactly as

@@ -401,6 +401,13 @@ class HipBLS:
         _check(self.lib.hipbls_verify_batch_keys(idx, blob, offs, b"".join(sigs), n, st), self.lib)
         return list(st)[:n]
 
+    def verify_keys(self, key_idx: int, data: bytes, signature: bytes) -> None:
+        """verify with the public key named by its index in the loaded table: the lone keyed call (the latency route,
+        H(m) read from and inserted into the H(m) cache).  Raises TBLSError as verify does."""
+        st = self.batch_verify_keys_status([key_idx], [data], [signature])[0]
+        if st != OK:
+            raise TBLSError(VERIFY_ERRORS[st])
+
     def batch_verify_rlc_keys_status(self, key_idx: Sequence[int], msgs: Sequence[bytes], sigs: Sequence[bytes],
                                      seed: Optional[bytes] = None) -> List[int]:
         """batch_verify_rlc_status with pks[i] = loaded table[key_idx[i]]."""

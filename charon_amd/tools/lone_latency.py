@@ -15,6 +15,14 @@ The sigagg_keys_* shapes are the same duties through hipbls_threshold_aggregate_
 resident table, the H(m) cache enabled and warmed by one keyed RLC BatchVerify over the duty's partials (what parsigex
 has done by the time charon aggregates); sigagg_keys_7of10_nocache runs with cache capacity 0, so the call hashes the
 root itself.
+
+The verify_keys_* shapes are the lone tbls.Verify by key index (hipbls_verify_batch_keys): _cold
+empties the H(m) cache before every call (outside the clock), so the call misses and inserts; _warm repeats the call on
+a cached root.  verify_keys_n<N> are N items over N / 4 roots with the cache disabled (every root hashed by the call),
+verify_keys_n<N>_warm the same on cached roots.  queued_verify_keyed_* is a lone hipbls_verify with the table loaded
+and the cache enabled, the Go binding's configuration.  chain_verify_keys_sigagg_keys_x2 is the proposer chain with
+keyed Verify and keyed sigagg and no warm-up call: the cache is emptied before every chain, the first Verify of each
+root inserts and the sigagg that follows hits.  --shapes takes name prefixes (comma-separated) to run a subset.
 """
 import argparse
 import ctypes
@@ -30,7 +38,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 R_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 STAGES = ("verify_prep8", "verify_pair_lq16", "verify_pair_lq8", "fav_prep8", "fav_lq16", "fav", "tv_prep8", "tv_lq16",
           "tagg_sum8", "tv_phase_a", "tv_prep_pk", "tagg_scale", "tagg_sum", "tv_check_unscale", "tagg_unscale",
-          "verify_pair_lq4", "verify_pair_lg2", "tv_prep8_keys", "tv_gather_keys", "tv_phase_a_keys")
+          "verify_pair_lq4", "verify_pair_lg2", "tv_prep8_keys", "tv_gather_keys", "tv_phase_a_keys",
+          "verify_prep8_keys", "verify_gather_keys", "verify_keys", "rlc_hash", "rlc_items", "rlc_window",
+          "rlc_window_lg2")
+SIZES = (8, 64, 512, 4096)
 
 
 def _duty(impl, rng, t, total):
@@ -45,7 +56,7 @@ def _duty(impl, rng, t, total):
     pubshares, st = impl.secret_to_public_key_batch([shares[i] for i in ids])
     assert set(st) == {0}
     return (dict(zip(ids, sigs)), impl.secret_to_public_key(secret), msg, impl.sign(secret, msg)), \
-        (dict(zip(ids, pubshares)), ids)
+        (dict(zip(ids, pubshares)), ids), [shares[i] for i in ids]
 
 
 def _fav(impl, rng, nkeys):
@@ -68,6 +79,7 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--timing-calls", type=int, default=20)
+    ap.add_argument("--shapes", default="", help="comma-separated name prefixes; default: every shape")
     a = ap.parse_args()
     if a.calls < 200:
         ap.error("--calls must be at least 200")
@@ -76,6 +88,7 @@ def main():
     rng = random.Random(0x10E)
     made = [_duty(impl, rng, 4, 6), _duty(impl, rng, 7, 10), _duty(impl, rng, 7, 10)]
     (d46, d710, d710b), shares = [m[0] for m in made], [m[1] for m in made]
+    share_secrets = made[0][2]  # duty 0's four share secrets, in the order of its sorted ids
     fav4, fav12 = _fav(impl, rng, 4), _fav(impl, rng, 12)
 
     def verify(d):  # a Verify of the duty's aggregate: the randao / block signature check
@@ -129,17 +142,64 @@ def main():
         verify(d710b)
         sigagg_keys(2)
 
+    def verify_keys(k):  # the same check as verify(duties[k]), the key by its table index
+        d = duties[k]
+        assert impl.batch_verify_keys_status([root_idx[k]], [d[2]], [d[3]]) == [0]
+
+    def verify_queued(k):
+        d = duties[k]
+        assert impl.verify_queued(d[1], d[2], d[3]) == 0
+
+    def chain_keys_all():
+        verify_keys(1)
+        sigagg_keys(1)
+        verify_keys(2)
+        sigagg_keys(2)
+
+    # N items over N / 4 roots: partial signatures of duty 0's four shares (their pubshares are table entries)
+    ids0 = sorted(d46[0])
+    sk_rng = random.Random(0x51E)
+    big = {}
+    for n in SIZES:
+        roots = [sk_rng.randbytes(32) for _ in range(max(1, n // 4))]
+        msgs = [roots[i // 4 % len(roots)] for i in range(n)]
+        big[n] = ([share_idx[0][ids0[i % 4]] for i in range(n)], msgs,
+                  impl.sign_batch([share_secrets[i % 4] for i in range(n)], msgs)[0])
+
+    def verify_keys_n(n):
+        kidx, msgs, sigs = big[n]
+        assert impl.batch_verify_keys_status(kidx, msgs, sigs) == [0] * n
+
     shapes = [("verify_1", lambda: verify(d710)), ("fav_1x4", lambda: fav(fav4)), ("fav_1x12", lambda: fav(fav12)),
               ("sigagg_4of6", lambda: sigagg(d46)), ("sigagg_7of10", lambda: sigagg(d710)),
               ("tagg_7of10", lambda: tagg(d710)), ("chain_verify_sigagg_x2", chain),
               ("sigagg_keys_4of6", lambda: sigagg_keys(0)), ("sigagg_keys_7of10", lambda: sigagg_keys(1)),
-              ("sigagg_keys_7of10_nocache", lambda: sigagg_keys(1)), ("chain_verify_sigagg_keys_x2", chain_keys)]
+              ("sigagg_keys_7of10_nocache", lambda: sigagg_keys(1)), ("chain_verify_sigagg_keys_x2", chain_keys),
+              ("verify_keys_1_cold", lambda: verify_keys(1)), ("verify_keys_1_warm", lambda: verify_keys(1)),
+              ("verify_keys_1_nocache", lambda: verify_keys(1)),
+              ("queued_verify_keyed_cold", lambda: verify_queued(1)),
+              ("queued_verify_keyed_warm", lambda: verify_queued(1)),
+              ("chain_verify_keys_sigagg_keys_x2", chain_keys_all)]
+    for n in SIZES:
+        shapes.append(("verify_keys_n%d" % n, lambda n=n: verify_keys_n(n)))
+        shapes.append(("verify_keys_n%d_warm" % n, lambda n=n: verify_keys_n(n)))
+    if a.shapes:
+        shapes = [s for s in shapes if s[0].startswith(tuple(a.shapes.split(",")))]
     # the cache state each shape runs in (set before its warm-up and again before its clocked and timed passes)
     setup = {"sigagg_keys_4of6": lambda: cache(65536, (0,)), "sigagg_keys_7of10": lambda: cache(65536, (1,)),
-             "sigagg_keys_7of10_nocache": lambda: cache(0), "chain_verify_sigagg_keys_x2": lambda: cache(65536, (1, 2))}
+             "sigagg_keys_7of10_nocache": lambda: cache(0), "chain_verify_sigagg_keys_x2": lambda: cache(65536, (1, 2)),
+             "verify_keys_1_warm": lambda: cache(65536), "verify_keys_1_nocache": lambda: cache(0),
+             "queued_verify_keyed_warm": lambda: cache(65536)}
+    for n in SIZES:
+        setup["verify_keys_n%d" % n] = lambda: cache(0)
+        setup["verify_keys_n%d_warm" % n] = lambda: cache(65536)
+    # run before every call of the shape, outside the clock: an empty cache, so every root is seen for the first time
+    before = {"verify_keys_1_cold": lambda: cache(65536), "queued_verify_keyed_cold": lambda: cache(65536),
+              "chain_verify_keys_sigagg_keys_x2": lambda: cache(65536)}
     for name, fn in shapes:
         setup.get(name, lambda: None)()
         for _ in range(a.warmup):
+            before.get(name, lambda: None)()
             fn()
     out = {"lib": os.environ.get("HIPBLS_LIB") or "in-tree", "build_id": tbls.build_id().get("src", "")[:16],
            "calls": a.calls, "warmup": a.warmup, "shapes": {}, "kernels_ms": {}}
@@ -147,6 +207,7 @@ def main():
         setup.get(name, lambda: None)()
         ms = []
         for _ in range(a.calls):
+            before.get(name, lambda: None)()
             t0 = time.perf_counter()
             fn()
             ms.append((time.perf_counter() - t0) * 1e3)
@@ -161,6 +222,7 @@ def main():
             setup.get(name, lambda: None)()
             impl.lib.hipbls_kernel_timing_reset()
             for _ in range(a.timing_calls):
+                before.get(name, lambda: None)()
                 fn()
             per = {}
             for st in STAGES:

@@ -144,7 +144,10 @@ int hipbls_verify_wait(uint64_t ticket, int32_t* status);
  * devices.  An item goes to the device its message hashes to, so the partials of one signing root meet in one
  * batch.  A batch of >= 8 items whose keys are all in the resident pubshare table runs as an RLC BatchVerify with
  * keys by index over its distinct messages, through the H(m) cache (statuses unchanged); the number of batches
- * that took this keyed path is hipbls_queue_keyed_batches. */
+ * that took this keyed path is hipbls_queue_keyed_batches.  With the H(m) cache enabled, keyed batches below 8
+ * items (a serial caller's lone Verify) run keyed too and count the same way, but on hipbls_verify_batch_keys'
+ * latency route instead of an RLC check: octets / sixteen lanes, H(m) from the cache, a miss inserted
+ * (HIPBLS_LAT_VERIFY_KEYS=0: the RLC path as before). */
 int hipbls_queue_config(uint64_t max_batch, uint32_t gather_us);
 int hipbls_queue_stats(uint64_t* batches, uint64_t* items);
 int hipbls_queue_keyed_batches(uint64_t* batches);
@@ -235,7 +238,15 @@ int hipbls_batch_verify_rlc(const uint8_t* pks, const uint8_t* sigs, const uint3
  * return exactly what the wire-format calls return for the same key bytes. */
 int hipbls_pubshare_table_load(const uint8_t* pks, uint64_t n, int32_t* status);
 int hipbls_pubshare_table_size(uint64_t* n);
-/* hipbls_verify_batch with pks[i] = table[key_idx[i]]; HIPBLS_ERR_ARG when an index is outside the table. */
+/* hipbls_verify_batch with pks[i] = table[key_idx[i]]; HIPBLS_ERR_ARG when an index is outside the table.
+ * Batches the wire-format call would run on octets (AUTO up to 4,096 items, sixteen lanes up to 4; forced
+ * HIPBLS_PAIR_OCTETS) take the same latency route with the keys copied from the table: each DISTINCT message is
+ * looked up in the context's H(m) cache (hipbls_hcache_config; counted per distinct message per call in
+ * hipbls_hcache_stats), a hit is read from its column, a miss is hashed once and INSERTED (on the proposer path the
+ * lone Verify is the first call to see a root; the keyed sigagg that follows hits).  With the cache disabled or smaller
+ * than the call's distinct messages, each is hashed once into a table of the call's own.  Statuses are unchanged in
+ * every case.  Other pair modes, larger batches and HIPBLS_LAT_VERIFY_KEYS=0 keep one lane per item ("verify_keys"),
+ * which leaves the cache alone.  Timed as "verify_prep8_keys" + "verify_gather_keys" + the check's name. */
 int hipbls_verify_batch_keys(const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* msg_offsets,
                              const uint8_t* sigs, uint64_t n, int32_t* status);
 /* hipbls_batch_verify_rlc with pks[i] = table[key_idx[i]]. */
@@ -368,7 +379,8 @@ int hipbls_batch_verify_rlc_keys_device(const uint32_t* d_key_idx, const uint8_t
  * (k_verify_fused), "verify_prep" + "verify_pair_lg2" (lane-pair Verify), "verify_keys", "rlc_items",
  * "rlc_hash", "rlc_window" / "rlc_window_lg2", "rlc_fallback" / "rlc_fallback_lg2", "tagg_scale", "tagg_sum",
  * "fav"; sigagg in one call: "tv_phase_a", "tv_check_unscale", "tv_prep8", "tv_lq16", and with keys by index
- * "tv_phase_a_keys", "tv_prep8_keys", "tv_gather_keys". */
+ * "tv_phase_a_keys", "tv_prep8_keys", "tv_gather_keys"; the keyed Verify latency route: "verify_prep8_keys",
+ * "verify_gather_keys" (then "verify_pair_lq16" / "verify_pair_lq8" as the wire-format call). */
 int hipbls_kernel_timing(const char* name, double* avg_ms, uint64_t* launches);
 int hipbls_kernel_timing_reset(void);
 
