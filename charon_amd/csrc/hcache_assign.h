@@ -26,10 +26,32 @@ inline void hcache_reset(HCacheState& hc, uint64_t cap) {
   hc.cap = cap;
 }
 
+// The distinct messages of n items in first-use order (umsg / uoff) and each item's index among them: the message
+// table that hcache_assign takes (the keyed Verify latency route, the queue's keyed batches, the prefetch).
+inline void distinct_messages(const uint8_t* msgs, const uint64_t* offs, uint64_t n, std::vector<uint8_t>& umsg,
+                              std::vector<uint64_t>& uoff, std::vector<uint32_t>& mid) {
+  std::unordered_map<std::string, uint32_t> pos;
+  mid.resize(n);
+  umsg.clear();
+  uoff.assign(1, 0);
+  for (uint64_t i = 0; i < n; ++i) {
+    std::string key((const char*)msgs + offs[i], offs[i + 1] - offs[i]);
+    auto it = pos.find(key);
+    if (it == pos.end()) {
+      it = pos.emplace(std::move(key), (uint32_t)(uoff.size() - 1)).first;
+      umsg.insert(umsg.end(), msgs + offs[i], msgs + offs[i + 1]);
+      uoff.push_back(umsg.size());
+    }
+    mid[i] = it->second;
+  }
+}
+
 // Assigns cache columns for the n_msgs distinct messages of one call: fills slot[m] and the list of messages that
 // must be hashed (misses).  Returns false (cache bypassed) when disabled or the call has more messages than slots.
+// count = false is the prefetch's form (hipbls_hcache_prefetch): the same slots, ring and map, but the hits / misses
+// counters stay put, since they describe the calls that consume H(m).
 inline bool hcache_assign(HCacheState& hc, const uint8_t* msgs, const uint64_t* offs, uint64_t n_msgs,
-                          std::vector<uint32_t>& slot, std::vector<uint32_t>& miss) {
+                          std::vector<uint32_t>& slot, std::vector<uint32_t>& miss, bool count = true) {
   if (hc.cap == 0 || n_msgs > hc.cap) return false;
   slot.assign(n_msgs, 0);
   miss.clear();
@@ -58,7 +80,7 @@ inline bool hcache_assign(HCacheState& hc, const uint8_t* msgs, const uint64_t* 
   }
   for (uint64_t m = 0; m < n_msgs; ++m) {
     if (hit[m]) {
-      hc.hits += 1;
+      if (count) hc.hits += 1;
       continue;
     }
     // messages are distinct within a call (the caller's message table), so each miss takes its own slot
@@ -74,7 +96,7 @@ inline bool hcache_assign(HCacheState& hc, const uint8_t* msgs, const uint64_t* 
     hc.map[keys[m]] = s;
     slot[m] = s;
     miss.push_back((uint32_t)m);
-    hc.misses += 1;
+    if (count) hc.misses += 1;
   }
   return true;
 }

@@ -88,6 +88,8 @@ __global__ void k_tv_prep8_keys(const uint32_t* key_idx, uint64_t T, const int32
 __global__ void k_verify_prep8_keys(const uint8_t* msgs, const uint64_t* moffs, const uint32_t* mlist, uint64_t n_hash,
                                     const uint32_t* hslot, uint32_t* H, uint64_t hstride, const uint8_t* sigs,
                                     uint64_t n, uint32_t* ws);
+__global__ void k_hcache_fill8(const uint8_t* msgs, const uint64_t* moffs, const uint32_t* mlist, uint64_t n_hash,
+                               const uint32_t* hslot, uint32_t* H, uint64_t hstride);
 }  // namespace bls_fp2p
 // The sixteen-lane check for batches of at most four items (verify_hex.hip: BLS_FP2_PAIR + BLS_HEX, namespace bls_hex).
 namespace bls_hex {
@@ -245,6 +247,9 @@ struct Context {
   // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
   // the call's own H(m) table and its prep + check workspace; used under the lock up to the call's stream sync
   DevBuf vk_midx, vk_slot, vk_mlist, vk_h, vk_ws;
+  // hipbls_hcache_prefetch's own messages, offsets, cache columns and miss list (used under the lock up to the call's
+  // stream sync; shared with no other call, so the prefetch needs no workspace ordering against them)
+  DevBuf pf_msg, pf_off, pf_slot, pf_mlist;
   // sigagg in one call (launch_tagg_verify): two workspace sets used alternately, each with the completion event of
   // the call that last used it
   DevBuf tv_pts[2], tv_pst[2], tv_ws[2], tv_aux[2];
@@ -460,7 +465,7 @@ const KernelRef kKernels[] = {
     KREF16(k_verify_pair_lq16), KREF8(k_fav_prep8), KREF16W(k_fav_pair_lq16),
     KREF8(k_tv_prep8), KREF8(k_tagg_sum8), KREF16(k_tv_pair_lq16),
     KREF(k_tv_phase_a_keys), KREF(k_tv_join_keys), KREF(k_tv_gather_keys), KREF8(k_tv_prep8_keys),
-    KREF(k_verify_gather_keys), KREF8(k_verify_prep8_keys),
+    KREF(k_verify_gather_keys), KREF8(k_verify_prep8_keys), KREF8(k_hcache_fill8),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -2053,24 +2058,7 @@ bool initial_lat_verify_keys() {
 const bool g_lat_verify_keys = initial_lat_verify_keys();
 bool use_verify_keys_lat(uint64_t n) { return g_lat_verify_keys && use_octets(n); }
 
-// The distinct messages of n items in first-use order (umsg / uoff) and each item's index among them.
-void distinct_messages(const uint8_t* msgs, const uint64_t* offs, uint64_t n, std::vector<uint8_t>& umsg,
-                       std::vector<uint64_t>& uoff, std::vector<uint32_t>& mid) {
-  std::unordered_map<std::string, uint32_t> pos;
-  mid.resize(n);
-  umsg.clear();
-  uoff.assign(1, 0);
-  for (uint64_t i = 0; i < n; ++i) {
-    std::string key((const char*)msgs + offs[i], offs[i + 1] - offs[i]);
-    auto it = pos.find(key);
-    if (it == pos.end()) {
-      it = pos.emplace(std::move(key), (uint32_t)(uoff.size() - 1)).first;
-      umsg.insert(umsg.end(), msgs + offs[i], msgs + offs[i + 1]);
-      uoff.push_back(umsg.size());
-    }
-    mid[i] = it->second;
-  }
-}
+// distinct_messages (the distinct messages of n items in first-use order): hcache_assign.h.
 
 // One context (lock held), stream `s`, the caller's buffers; returns after the stream has drained, so a column found
 // in the cache's map has been written and every read of a column here is over before the lock is released.
@@ -2152,6 +2140,76 @@ int verify_keys_lat(Context& c, VkBufs B, hipStream_t s, const uint32_t* key_idx
   HIP_TRY(hipMemcpyAsync(status, B.st->p, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   undo.on = false;
+  return HIPBLS_OK;
+}
+
+// ============================================================================ H(m) prefetch
+// hipbls_hcache_prefetch on one context (lock held): the distinct roots umsg / uoff that the cache does not hold are
+// hashed into ring columns on the library stream, from the prefetch's own buffers.  A third writer of
+// the shared cache under the rule of the other two (rlc_host_on, verify_keys_lat): assign under the lock, wait for the
+// keyed sigagg's last gather (tv_hread) before a column is overwritten, and return only after the stream has drained,
+// so a root found in the map by the next lock holder has its column written.  Up to kLq8MaxVerify misses take octets
+// (verify_lat.hip k_hcache_fill8), more take one lane per message (k_rlc_hash).  The counters of hipbls_hcache_stats do
+// not move: they describe the calls that consume H(m).  Bypassed (nothing launched, nothing counted) exactly where
+// hcache_assign bypasses.
+int hcache_prefetch_on(Context& c, const uint8_t* umsg, const uint64_t* uoff, uint64_t n_msgs, uint64_t& hashed,
+                       uint64_t& present) {
+  hashed = present = 0;
+  std::vector<uint32_t> slot, miss;
+  if (!hcache_assign(c.hcache, umsg, uoff, n_msgs, slot, miss, false)) return HIPBLS_OK;
+  if (miss.empty()) {
+    present = n_msgs;
+    return HIPBLS_OK;
+  }
+  const hipStream_t s = c.stream;
+  // Every exit but the last drains the stream (no queued copy reads a freed host vector) and takes this call's misses
+  // out of the map again: their columns may never have been written.
+  struct Undo {
+    Context& c;
+    hipStream_t s;
+    const uint8_t* umsg;
+    const uint64_t* uoff;
+    const std::vector<uint32_t>&slot, &miss;
+    bool on = true;
+    ~Undo() {
+      if (!on) return;
+      (void)hipStreamSynchronize(s);
+      hcache_erase_misses(c.hcache, umsg, uoff, slot, miss);
+    }
+  } undo{c, s, umsg, uoff, slot, miss};
+  const uint64_t msg_total = uoff[n_msgs], n_hash = miss.size();
+  HIP_TRY(c.pf_msg.ensure(msg_total ? msg_total : 1));
+  HIP_TRY(c.pf_off.ensure((n_msgs + 1) * 8));
+  HIP_TRY(c.pf_slot.ensure(n_msgs * 4));
+  HIP_TRY(c.pf_mlist.ensure(n_hash * 4));
+  // a keyed sigagg call that released the lock may still be gathering H(m) from columns the misses are about to take
+  if (c.tv_hread) HIP_TRY(hipStreamWaitEvent(s, c.tv_hread, 0));
+  if (msg_total) HIP_TRY(hipMemcpyAsync(c.pf_msg.p, umsg, msg_total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.pf_off.p, uoff, (n_msgs + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.pf_slot.p, slot.data(), n_msgs * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.pf_mlist.p, miss.data(), n_hash * 4, hipMemcpyHostToDevice, s));
+  const uint8_t* dmsg = (const uint8_t*)c.pf_msg.p;
+  const uint64_t* doff = (const uint64_t*)c.pf_off.p;
+  const uint32_t *dslot = (const uint32_t*)c.pf_slot.p, *dmiss = (const uint32_t*)c.pf_mlist.p;
+  uint32_t* dH = (uint32_t*)c.hcache.table.p;
+  const uint64_t stride = c.hcache.cap;
+  int rc;
+  if (n_hash <= kLq8MaxVerify) {
+    rc = timed(c, "hcache_fill8", s, [&] {
+      hipLaunchKernelGGL(bls_fp2p::k_hcache_fill8, dim3((unsigned)grid_for(8 * n_hash)), dim3(kBlock), 0, s, dmsg,
+                         doff, dmiss, n_hash, dslot, dH, stride);
+    });
+  } else {
+    rc = timed(c, "rlc_hash", s, [&] {
+      hipLaunchKernelGGL(k_rlc_hash, dim3((unsigned)grid_for(n_hash)), dim3(kBlock), 0, s, dmsg, doff, n_hash, dmiss,
+                         dH, stride, dslot);
+    });
+  }
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  undo.on = false;
+  hashed = n_hash;
+  present = n_msgs - n_hash;
   return HIPBLS_OK;
 }
 
@@ -3557,6 +3615,33 @@ int hipbls_hcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries) {
     *hits += c.hcache.hits;
     *misses += c.hcache.misses;
     *entries += c.hcache.map.size();
+  }
+  return HIPBLS_OK;
+}
+
+// Every context's cache gets the roots (one host thread per context, run_all): a lone host call lands on the first
+// context and a queued hipbls_verify on the context its message hashes to, and both must hit.
+int hipbls_hcache_prefetch(const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t n_msgs, uint64_t* hashed,
+                           uint64_t* present) {
+  if (hashed) *hashed = 0;
+  if (present) *present = 0;
+  if (n_msgs == 0) return HIPBLS_OK;
+  if (!msg_offsets || !offsets_ok(msg_offsets, n_msgs)) return arg_err("bad message offsets");
+  if (msg_offsets[n_msgs] && !msgs) return arg_err("null messages");
+  ENSURE_INIT();
+  std::vector<uint8_t> umsg;
+  std::vector<uint64_t> uoff;
+  std::vector<uint32_t> mid;
+  distinct_messages(msgs, msg_offsets, n_msgs, umsg, uoff, mid);
+  const int nc = nctx();
+  std::vector<uint64_t> h(nc, 0), p(nc, 0);
+  int rc = run_all([&](Context& c) -> int {
+    return hcache_prefetch_on(c, umsg.data(), uoff.data(), uoff.size() - 1, h[c.slot], p[c.slot]);
+  });
+  if (rc) return rc;
+  for (int k = 0; k < nc; ++k) {
+    if (hashed) *hashed += h[k];
+    if (present) *present += p[k];
   }
   return HIPBLS_OK;
 }

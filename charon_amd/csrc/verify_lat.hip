@@ -165,6 +165,29 @@ __global__ void __launch_bounds__(kOctBlock) k_verify_prep8_keys(
   }
 }
 
+// The hash role of k_verify_prep8_keys alone, for roots that are known before any signature over them exists
+// (hipbls_hcache_prefetch; hipbls.hip hcache_prefetch_on): one octet per message of the miss list (mlist, or
+// 0 .. n_hash - 1 without one), H(m) into column hslot[m] of the context's H(m) cache (stride hstride).  A kernel of its
+// own so that its timing row ("hcache_fill8") tells prefetched hashes from a Verify's own.  Not raced: replicas would
+// all store into a shared cache column.
+__global__ void __launch_bounds__(kOctBlock) k_hcache_fill8(
+    const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ moffs, const uint32_t* __restrict__ mlist,
+    uint64_t n_hash, const uint32_t* __restrict__ hslot, uint32_t* __restrict__ H, uint64_t hstride) {
+  bls_race::init(nullptr, 0u);
+  const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t i = t >> 3;
+  if (i >= n_hash) return;  // the same on all eight lanes
+  const uint32_t m = (t & 1) ? ~0u : 0u;
+  const uint64_t msg = mlist ? mlist[i] : i;
+  const uint64_t o0 = moffs[msg], o1 = moffs[msg + 1];
+  g2j sum, hj;
+  hash_to_g2_pair_sum(sum, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, m);
+  g2_clear_cofactor_quad(hj, sum, (int)(t & 3));
+  g2a hm;
+  jac_to_aff(hm, hj);
+  if ((t & 7) == 0) soa_store<48>(H, hstride, h_col(hslot, msg), &hm.x.c0.v[0]);
+}
+
 // FastAggregateVerify's stage 1 for a few groups (tbls/herumi.go:315-339; hipbls.hip launch_fav, the sync committee's
 // one aggregate per slot), eight lanes per unit: every key of every group decoded + subgroup-tested (pts: affine SoA
 // with stride nkeys, kcode: DEC_* per key), beside each group's signature decode and message hash exactly as

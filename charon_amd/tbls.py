@@ -91,6 +91,7 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_aggregate_device": ([vp, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_hcache_config": ([u64], ctypes.c_int),
         "hipbls_hcache_stats": ([u64p, u64p, u64p], ctypes.c_int),
+        "hipbls_hcache_prefetch": ([u8p, u64p, u64, u64p, u64p], ctypes.c_int),
         "hipbls_keycache_config": ([u64], ctypes.c_int),
         "hipbls_keycache_stats": ([u64p, u64p, u64p], ctypes.c_int),
         "hipbls_abi_version": ([], ctypes.c_int),
@@ -159,7 +160,7 @@ def exported_symbols() -> List[str]:
         "hipbls_rlc_set_g1_msm_min", "hipbls_scratch_budget", "hipbls_stream_joins", "hipbls_kernel_names",
         "hipbls_queue_worker_stats", "hipbls_set_latency_replicas", "hipbls_build_id",
         "hipbls_threshold_aggregate_verify_batch_keys", "hipbls_threshold_aggregate_verify_batch_keys_device",
-        "hipbls_keycache_config", "hipbls_keycache_stats",
+        "hipbls_keycache_config", "hipbls_keycache_stats", "hipbls_hcache_prefetch",
     ]
 
 
@@ -668,6 +669,15 @@ class HipBLS:
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self.lib.hipbls_hcache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), self.lib)
         return a.value, b.value, c.value
+
+    def hcache_prefetch(self, msgs: Sequence[bytes]) -> Tuple[int, int]:
+        """Hash signing roots into the H(m) cache ahead of their first signature (hipbls_hcache_prefetch): returns
+        (hashed, present), summed over contexts; (0, 0) when the cache is off or smaller than the distinct roots.
+        hcache_stats' hits / misses do not move."""
+        blob, offs = _offsets(msgs)
+        h, p = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self.lib.hipbls_hcache_prefetch(blob, offs, len(msgs), ctypes.byref(h), ctypes.byref(p)), self.lib)
+        return h.value, p.value
 
     # ---------------------------------------------------------------- resident key cache (wire-format calls)
     def keycache_config(self, slots: int) -> None:

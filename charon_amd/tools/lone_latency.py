@@ -22,7 +22,19 @@ a cached root.  verify_keys_n<N> are N items over N / 4 roots with the cache dis
 verify_keys_n<N>_warm the same on cached roots.  queued_verify_keyed_* is a lone hipbls_verify with the table loaded
 and the cache enabled, the Go binding's configuration.  chain_verify_keys_sigagg_keys_x2 is the proposer chain with
 keyed Verify and keyed sigagg and no warm-up call: the cache is emptied before every chain, the first Verify of each
-root inserts and the sigagg that follows hits.  --shapes takes name prefixes (comma-separated) to run a subset.
+root inserts and the sigagg that follows hits.
+
+The prefetch shapes (hipbls_hcache_prefetch): prefetch_<N> is the call itself over N roots the cache
+does not hold (emptied before every call, outside the clock; 4,097 roots take the one-lane route).  The *_prefetched
+shapes are verify_keys_1_cold, queued_verify_keyed_cold and the keyed chain with each root prefetched outside the
+clock, after the cache was emptied and before the root's first Verify.  verify_keys_1_warm_beside_prefetch_<N> is the
+warm lone Verify while another thread issues prefetch calls of N fresh roots back to back: what the prefetch's hold of
+the context lock costs a caller that collides with it (the other thread also takes Python's interpreter lock between
+its calls, so the row is an upper bound).  Back to back, the two threads take the context lock (an unfair mutex) in long
+turns, so the row's max_ms and pass_wall_ms show starvation rather than one collision; the _beside_paced_prefetch_<N>
+rows rest the other thread 5 ms between its calls, so that a clocked call waits for at most one prefetch.
+
+--shapes takes name prefixes (comma-separated) to run a subset.
 """
 import argparse
 import ctypes
@@ -31,6 +43,7 @@ import os
 import random
 import statistics
 import sys
+import threading
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -40,8 +53,11 @@ STAGES = ("verify_prep8", "verify_pair_lq16", "verify_pair_lq8", "fav_prep8", "f
           "tagg_sum8", "tv_phase_a", "tv_prep_pk", "tagg_scale", "tagg_sum", "tv_check_unscale", "tagg_unscale",
           "verify_pair_lq4", "verify_pair_lg2", "tv_prep8_keys", "tv_gather_keys", "tv_phase_a_keys",
           "verify_prep8_keys", "verify_gather_keys", "verify_keys", "rlc_hash", "rlc_items", "rlc_window",
-          "rlc_window_lg2")
+          "rlc_window_lg2", "hcache_fill8")
 SIZES = (8, 64, 512, 4096)
+PREFETCH_SIZES = (1, 64, 4097)
+BESIDE_SIZES = (1, 4096)
+PACED_PAUSE_S = 0.005  # the paced collision rows: the other thread rests this long between its prefetch calls
 
 
 def _duty(impl, rng, t, total):
@@ -170,6 +186,43 @@ def main():
         kidx, msgs, sigs = big[n]
         assert impl.batch_verify_keys_status(kidx, msgs, sigs) == [0] * n
 
+    # prefetch: N fresh 32-byte roots per call, straight through the C call (no per-root Python work in the clock)
+    pf_offs = {n: (ctypes.c_uint64 * (n + 1))(*range(0, 32 * n + 1, 32)) for n in set(PREFETCH_SIZES + BESIDE_SIZES)}
+
+    def prefetch_n(n, want_hashed=True):
+        h, p = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = impl.lib.hipbls_hcache_prefetch(os.urandom(32 * n), pf_offs[n], n, ctypes.byref(h), ctypes.byref(p))
+        assert rc == 0 and (not want_hashed or (h.value, p.value) == (n, 0)), (rc, h.value, p.value)
+
+    def prefetched(ks):  # an empty cache, then the duties' roots hashed ahead of their first Verify
+        cache(65536)
+        assert impl.hcache_prefetch([duties[k][2] for k in ks]) == (len(ks), 0)
+
+    # the collision rows: a thread that prefetches fresh roots back to back while the shape's calls are clocked
+    beside = {"stop": None, "thread": None, "ms": []}
+
+    def beside_start(n, capacity, pause_s=0.0):
+        cache(capacity)
+        verify_keys(1)  # the clocked root is warm
+        beside["stop"] = threading.Event()
+        beside["ms"] = []
+
+        def loop():
+            while not beside["stop"].is_set():
+                t0 = time.perf_counter()
+                prefetch_n(n)
+                beside["ms"].append((time.perf_counter() - t0) * 1e3)
+                if pause_s:
+                    time.sleep(pause_s)
+
+        beside["thread"] = threading.Thread(target=loop)
+        beside["thread"].start()
+
+    def beside_stop():
+        beside["stop"].set()
+        beside["thread"].join()
+        return _stats(beside["ms"]) if beside["ms"] else {"calls": 0}
+
     shapes = [("verify_1", lambda: verify(d710)), ("fav_1x4", lambda: fav(fav4)), ("fav_1x12", lambda: fav(fav12)),
               ("sigagg_4of6", lambda: sigagg(d46)), ("sigagg_7of10", lambda: sigagg(d710)),
               ("tagg_7of10", lambda: tagg(d710)), ("chain_verify_sigagg_x2", chain),
@@ -183,6 +236,14 @@ def main():
     for n in SIZES:
         shapes.append(("verify_keys_n%d" % n, lambda n=n: verify_keys_n(n)))
         shapes.append(("verify_keys_n%d_warm" % n, lambda n=n: verify_keys_n(n)))
+    for n in PREFETCH_SIZES:
+        shapes.append(("prefetch_%d" % n, lambda n=n: prefetch_n(n)))
+    shapes += [("verify_keys_1_prefetched", lambda: verify_keys(1)),
+               ("queued_verify_keyed_prefetched", lambda: verify_queued(1)),
+               ("chain_verify_keys_sigagg_keys_x2_prefetched", chain_keys_all)]
+    for n in BESIDE_SIZES:
+        shapes.append(("verify_keys_1_warm_beside_prefetch_%d" % n, lambda: verify_keys(1)))
+        shapes.append(("verify_keys_1_warm_beside_paced_prefetch_%d" % n, lambda: verify_keys(1)))
     if a.shapes:
         shapes = [s for s in shapes if s[0].startswith(tuple(a.shapes.split(",")))]
     # the cache state each shape runs in (set before its warm-up and again before its clocked and timed passes)
@@ -196,28 +257,49 @@ def main():
     # run before every call of the shape, outside the clock: an empty cache, so every root is seen for the first time
     before = {"verify_keys_1_cold": lambda: cache(65536), "queued_verify_keyed_cold": lambda: cache(65536),
               "chain_verify_keys_sigagg_keys_x2": lambda: cache(65536)}
+    for n in PREFETCH_SIZES:
+        before["prefetch_%d" % n] = lambda: cache(65536)
+    before["verify_keys_1_prefetched"] = before["queued_verify_keyed_prefetched"] = lambda: prefetched((1,))
+    before["chain_verify_keys_sigagg_keys_x2_prefetched"] = lambda: prefetched((1, 2))
+    # the other thread's roots must not push the clocked root out of the ring within a pass: 4,096 per call need room
+    after = {}
+    for n in BESIDE_SIZES:
+        setup["verify_keys_1_warm_beside_prefetch_%d" % n] = lambda n=n: beside_start(n, 65536 if n == 1 else 1 << 22)
+        after["verify_keys_1_warm_beside_prefetch_%d" % n] = beside_stop
+        setup["verify_keys_1_warm_beside_paced_prefetch_%d" % n] = \
+            lambda n=n: beside_start(n, 65536 if n == 1 else 1 << 22, PACED_PAUSE_S)
+        after["verify_keys_1_warm_beside_paced_prefetch_%d" % n] = beside_stop
     for name, fn in shapes:
         setup.get(name, lambda: None)()
         for _ in range(a.warmup):
             before.get(name, lambda: None)()
             fn()
+        after.get(name, lambda: None)()
     out = {"lib": os.environ.get("HIPBLS_LIB") or "in-tree", "build_id": tbls.build_id().get("src", "")[:16],
            "calls": a.calls, "warmup": a.warmup, "shapes": {}, "kernels_ms": {}}
     for name, fn in shapes:
         setup.get(name, lambda: None)()
         ms = []
+        wall0 = time.perf_counter()
         for _ in range(a.calls):
             before.get(name, lambda: None)()
             t0 = time.perf_counter()
             fn()
             ms.append((time.perf_counter() - t0) * 1e3)
+        wall = (time.perf_counter() - wall0) * 1e3
         out["shapes"][name] = _stats(ms)
+        if name in after:
+            out["shapes"][name]["max_ms"] = round(max(ms), 4)
+            out["shapes"][name]["prefetch_beside"] = after[name]()
+            out["shapes"][name]["pass_wall_ms"] = round(wall, 1)
+            h, m, _ = impl.hcache_stats()
+            out["shapes"][name]["verify_hits_misses"] = [h, m]
     # per-kernel averages, in a pass of their own: the event pairs around each launch are not in the clocked calls
     impl.lib.hipbls_kernel_timing_reset()
     impl.lib.hipbls_set_timing(1)
     try:
         for name, fn in shapes:
-            if name.startswith("chain_"):
+            if name.startswith("chain_") or name in after:
                 continue
             setup.get(name, lambda: None)()
             impl.lib.hipbls_kernel_timing_reset()

@@ -278,6 +278,19 @@ int hipbls_rlc_batch_stats(uint64_t* attempted, uint64_t* passed, int32_t* last)
  * Statuses are unchanged by the cache. */
 int hipbls_hcache_config(uint64_t capacity);
 int hipbls_hcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* entries);
+/* A hint: hash the n_msgs signing roots msgs[msg_offsets[m] .. msg_offsets[m+1]) into the H(m) cache before any
+ * signature over them exists (the randao root at epoch start, a duty's root once consensus has decided the unsigned
+ * data), so that the first hipbls_verify_batch_keys / queued hipbls_verify / keyed sigagg of each root is a hit.  The
+ * call touches no signature, key or status.  Duplicate roots are folded; each distinct root the cache does not hold is
+ * hashed on eight lanes ("hcache_fill8"; above 4,096 misses on one lane each, "rlc_hash") and inserted under the FIFO
+ * replacement of the other writers, in EVERY context's cache.  *hashed / *present (each may be null; summed over
+ * contexts): roots this call hashed and inserted / roots the cache already held.  The hits / misses of
+ * hipbls_hcache_stats do not move (they count consumers; a Verify after a prefetch shows up as a hit); entries does.
+ * With the cache disabled, or more distinct roots than its capacity, nothing is launched and both outputs are 0.  The
+ * call returns after the columns are written.  HIPBLS_ERR_ARG for null or non-monotone offsets or null msgs with a
+ * non-zero total; n_msgs == 0 is OK. */
+int hipbls_hcache_prefetch(const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t n_msgs, uint64_t* hashed,
+                           uint64_t* present);
 
 /* Resident key cache used by the wire-format calls (hipbls_verify_batch[_device], hipbls_batch_verify_rlc[_device],
  * the submission queue's wire batches): the kernels look each 48-byte public key up in a per-context table in HBM and,

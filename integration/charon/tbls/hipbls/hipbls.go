@@ -134,6 +134,34 @@ func ConfigHCache(capacity uint64) error {
 	return nil
 }
 
+// PrefetchRoots hashes signing roots into every GPU's H(m) cache before any signature over them exists
+// (hipbls_hcache_prefetch), so that the first Verify or BatchThresholdAggregateVerify of each root reads H(m) instead
+// of hashing it: the randao root at the start of an epoch, a duty's root once consensus has decided the unsigned data
+// (INTEGRATION.md "Prefetching roots" names the sites).  A hint: it touches no key, signature or verdict, roots the
+// cache already holds cost nothing, and with the cache disabled it does nothing.  It returns after the hashes are
+// written (about the time of one Verify), so call it from a goroutine that is not on the duty's critical path.
+func PrefetchRoots(roots [][]byte) error {
+	if len(roots) == 0 {
+		return nil
+	}
+	flat := make([]byte, 0, 32*len(roots))
+	offs := make([]uint64, len(roots)+1)
+	for i, r := range roots {
+		flat = append(flat, r...)
+		offs[i+1] = uint64(len(flat))
+	}
+	var msgs *C.uint8_t
+	if len(flat) > 0 {
+		msgs = (*C.uint8_t)(unsafe.Pointer(&flat[0]))
+	}
+	rc := C.hipbls_hcache_prefetch(msgs, (*C.uint64_t)(unsafe.Pointer(&offs[0])), C.uint64_t(len(roots)), nil, nil)
+	if rc != C.HIPBLS_OK {
+		return devErr(rc)
+	}
+
+	return nil
+}
+
 // LoadPubShares decodes and subgroup-checks the cluster's pubshares once into every GPU's resident table
 // (hipbls_pubshare_table_load; SURVEY.md §8f.2: the lock's keys, app/app.go:344-381).  Afterwards BatchVerify and
 // BatchVerifyRLC name keys by table index when every key of a call is in the table (no per-call decode or subgroup
