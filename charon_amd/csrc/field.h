@@ -314,7 +314,8 @@ BLS_HD BLS_INLINE void fp_mul_impl(fp& r, const fp& a, const fp& b) {
 // rather than a call, the only registers it must treat as clobbered are the ones the routine really
 // touches (v24-v39, s16-s31, vcc) -- not the ABI's whole caller-saved set -- so values live across
 // a product stay in registers instead of being saved to scratch around every multiplication.
-// Operands are pinned: a in v[0:11] (result out), b in v[12:23].
+// Operands are pinned: a in v[0:11] (result out), b in v[12:23]; the squaring (bls_fp_sqr_rt, bls_fp_sqr_run_rt)
+// takes a in v[0:11] and uses v12-v23 for the doubled operand.
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef uint32_t u32x12 __attribute__((ext_vector_type(12)));
 // Never called: hosts the routine's code (entered only at the local label).
@@ -324,7 +325,9 @@ __device__ __attribute__((used, noinline)) static void bls_fp_asm_routines() {
                ".p2align 6\n.type bls_fp2_mul_rt,@function\nbls_fp2_mul_rt:\n\t" BLS_FP2_MUL_ASM_BODY
                "\n\ts_setpc_b64 s[30:31]\n"
                ".p2align 6\n.type bls_fp2_sqr_rt,@function\nbls_fp2_sqr_rt:\n\t" BLS_FP2_SQR_ASM_BODY
-               "\n\ts_setpc_b64 s[30:31]\n");
+               "\n\ts_setpc_b64 s[30:31]\n"
+               // the squaring carries its own labels: two entries (one squaring; a run of s38 of them) and its return
+               ".p2align 6\n.type bls_fp_sqr_rt,@function\n.type bls_fp_sqr_run_rt,@function\n" BLS_FP_SQR_ASM_ROUTINE);
 }
 #ifndef BLS_LAZY_FP6
 #define BLS_LAZY_FP6 0
@@ -408,10 +411,22 @@ BLS_HD BLS_INLINE void fp_from_vec(fp& r, const u32x12& v) {
   r.v[6] = v.s6; r.v[7] = v.s7; r.v[8] = v.s8; r.v[9] = v.s9; r.v[10] = v.sA; r.v[11] = v.sB;
 }
 BLS_HD BLS_INLINE void fp_mul(fp& r, const fp& a, const fp& b) { fp_from_vec(r, fp_mul_dev(fp_to_vec(a), fp_to_vec(b))); }
-BLS_HD BLS_INLINE void fp_sqr(fp& r, const fp& a) {
-  const u32x12 v = fp_to_vec(a);
-  fp_from_vec(r, fp_mul_dev(v, v));
+// The squaring is a routine of its own (tools/gen_fp_asm.py gen_sqr: every cross product once), operand in v[0:11] in
+// and out.  fp_sqr_n squares n >= 1 times inside the routine (the count in s38): canonical after every squaring, so
+// it equals n calls bit for bit, without the call sequence and the operand moves in between.
+__device__ __forceinline__ static u32x12 fp_sqr_dev(u32x12 a) {
+  asm volatile(BLS_ASM_CALL("bls_fp_sqr_rt") : "+{v[0:11]}"(a) : BLS_P_SGPR_IN
+               : BLS_FP_SQR_ASM_CLOBBERS, "s38", BLS_CALL_CLOBBERS);
+  return a;
 }
+__device__ __forceinline__ static u32x12 fp_sqr_run_dev(u32x12 a, uint32_t n) {
+  n = __builtin_amdgcn_readfirstlane(n);  // wave-uniform by contract
+  asm volatile(BLS_ASM_CALL("bls_fp_sqr_run_rt") : "+{v[0:11]}"(a), "+{s38}"(n) : BLS_P_SGPR_IN
+               : BLS_FP_SQR_ASM_CLOBBERS, BLS_CALL_CLOBBERS);
+  return a;
+}
+BLS_HD BLS_INLINE void fp_sqr(fp& r, const fp& a) { fp_from_vec(r, fp_sqr_dev(fp_to_vec(a))); }
+BLS_HD BLS_INLINE void fp_sqr_n(fp& r, const fp& a, uint32_t n) { fp_from_vec(r, fp_sqr_run_dev(fp_to_vec(a), n)); }
 #else
 #if defined(BLS_HOST_FAST_MUL)
 // Host CPU baseline build (tests/native/cpu_baseline.cpp): the same Montgomery product (R = 2^384) on 6 x 64-bit
@@ -480,6 +495,10 @@ BLS_HD BLS_NOINLINE fp fp_sqr_v(fp a) {
 }
 BLS_HD BLS_INLINE void fp_mul(fp& r, const fp& a, const fp& b) { r = fp_mul_v(a, b); }
 BLS_HD BLS_INLINE void fp_sqr(fp& r, const fp& a) { r = fp_sqr_v(a); }
+BLS_HD BLS_INLINE void fp_sqr_n(fp& r, const fp& a, uint32_t n) {  // n >= 1 squarings (the device runs them in one call)
+  r = fp_sqr_v(a);
+  while (--n) r = fp_sqr_v(r);
+}
 #endif
 
 // r = a^e for a fixed exponent given as little-endian 32-bit limbs whose top set bit is top_bit.
@@ -545,20 +564,21 @@ BLS_HD BLS_CALL void fp_pow(fp& r, const fp& a, const uint32_t* e, int top_bit) 
   auto bit = [&](int i) { return (e[i >> 5] >> (i & 31)) & 1u; };
   fp acc;
   bool started = false;
+  uint32_t run = 0;  // squarings owed to acc: taken in one fp_sqr_n before the next product (or at the end)
   int i = top_bit;
   while (i >= 0) {
     if (!bit(i)) {
-      if (started) fp_sqr(acc, acc);
+      run += started;
       --i;
       continue;
     }
     int j = i - (W - 1) < 0 ? 0 : i - (W - 1);
     while (!bit(j)) ++j;  // window [i..j] ends on a set bit, so its value is odd
     uint32_t v = 0;
-    for (int k = i; k >= j; --k) {
-      v = (v << 1) | bit(k);
-      if (started) fp_sqr(acc, acc);
-    }
+    for (int k = i; k >= j; --k) v = (v << 1) | bit(k);
+    if (started) run += (uint32_t)(i - j + 1);
+    if (run) fp_sqr_n(acc, acc, run);
+    run = 0;
     // the table index is wave-uniform: select through a switch of constant indices so the table stays in
     // registers (a dynamic index would put it in scratch and cost a memory round trip per window)
     fp w;
@@ -586,6 +606,7 @@ BLS_HD BLS_CALL void fp_pow(fp& r, const fp& a, const uint32_t* e, int top_bit) 
     }
     i = j - 1;
   }
+  if (run) fp_sqr_n(acc, acc, run);  // the exponent's trailing zero bits
   r = acc;
 }
 

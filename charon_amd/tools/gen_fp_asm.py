@@ -1,4 +1,4 @@
-"""Generate charon_amd/csrc/fp_asm_gfx950.h: the gfx950 Montgomery product as one asm routine.
+"""Generate charon_amd/csrc/fp_asm_gfx950.h: the gfx950 Montgomery product and squaring as asm routines.
 
 SHIPPED (gen_mul): radix 2^32, 12 limbs, product scanning (Comba) with the Montgomery reduction
 interleaved per column.  Every limb product is one v_mad_u64_u32 into a 64-bit column accumulator,
@@ -9,6 +9,10 @@ and only v24-v39, s16-s28 and vcc are clobbered, so values live across a product
 The final select uses v_cndmask_b32_e64 with an explicit VCC operand: on gfx950 the VOP2 (e32) form that
 reads VCC implicitly issues at ~19 cycles per instruction against ~4.4 for the e64 form and for v_bfi_b32
 (profiles/r02_prod_probe.txt, tools/sel_probe.hip).
+
+SHIPPED (gen_sqr, gen_sqr_routine): the Fp squaring as a routine of its own in the same frame, every cross product
+taken once against a doubled operand (78 operand mads instead of 144; 469 instructions), with a second entry that
+squares n times without returning (the square-root chains of fp_pow).
 
 EXPERIMENT (gen_mul29, not emitted): radix 2^29, 14 limbs, R = 2^406, no carry capture (a column of
 <= 28 terms < 2^58 fits the 64-bit accumulator), two accumulator chains, lazy [0, 2p) output, list
@@ -242,20 +246,22 @@ M64 = (1 << 64) - 1
 PL32 = [(P >> (32 * i)) & 0xFFFFFFFF for i in range(N32)]
 
 
-def _comba(w, pairs, M, out, acc, elide=True):
+def _comba(w, pairs, M, out, acc, elide=True, col_terms=None):
     """Product scanning with the Montgomery reduction interleaved per column (radix 2^32, R = 2^384): appends
     r = (sum of X*Y over pairs)/R, raw, to the stream w.  pairs = [(X, Y)] (limb index -> register); M(i) holds the
     quotient digits; out(j) receives result limb j (from column j + 12; out(j) may alias a register dead by then).
     Accumulator v[acc:acc+1], the carried value (hi, carries) in v[acc+2:acc+3]; p in s16-s27, -p^-1 mod 2^32 in s28.
-    elide=False: every mad catches its carry (the round-5 streams, term for term)."""
+    elide=False: every mad catches its carry (the round-5 streams, term for term).
+    col_terms(i), when given, replaces the operand terms of column i (pairs is then unused): it returns
+    [(x register, y register, bound of x*y)] and may append instructions of its own to w first (gen_sqr)."""
     lo, hi, mv, cw = ("v%d" % (acc + k) for k in range(4))
     accp, srcp = "v[%d:%d]" % (acc, acc + 1), "v[%d:%d]" % (acc + 2, acc + 3)
     Sp = lambda j: "s%d" % (16 + j)
     n_prev = 0
     for i in range(2 * N32 - 1):
-        body = []
+        body = [] if col_terms is None else list(col_terms(i))
         for j in range(max(0, i - N32 + 1), min(i, N32 - 1) + 1):
-            for X, Y in pairs:
+            for X, Y in (pairs if col_terms is None else ()):
                 bx = TOP_BOUND if j == N32 - 1 else LIMB_MAX
                 by = TOP_BOUND if i - j == N32 - 1 else LIMB_MAX
                 body.append((X(j), Y(i - j), bx * by))
@@ -390,6 +396,68 @@ def gen_mul(e64_select=True, elide=None):
 
 
 gen_mul32 = gen_mul  # name used by tools/gen_probe_bodies.py
+
+
+# ---------------------------------------------------------------- Fp squaring (round 11)
+# a^2 with every cross product taken once.  With D = 2a as twelve limbs (D_k = a_k << 1 | a_(k-1) >> 31) and
+# E_(j+1) = a_(j+1) << 1 (32 bits; the bit shifted out is the low bit of D_(j+2)):
+#   a^2 = sum_j a_j^2 B^(2j) + sum_j a_j B^j (E_(j+1) B^(j+1) + sum_(k > j+1) D_k B^k)
+# since 2 (a >> 32 (j+1)) has the limbs E_(j+1), D_(j+2), .., D_11 and, for a < 2^383, nothing above.  78 operand mads
+# instead of 144, ten v_alignbit for D_2..D_11 (v14-v23, where gen_mul holds b) and eleven shifts for the E's, each
+# formed one column before the only column that reads it (2j + 1), alternately in v12 and v13.  Otherwise gen_mul's
+# frame: same columns, reduction, carry elision over the new column sums (D's and E's limbs reach 2^32 - 1,
+# D_11 < 2^31), in-place even columns, canonical output; a = v[0:11] in and out, v12-v39, vcc clobbered.
+SQR_RUN_SGPR = "s38"  # the run entry's count: outside s16-s28 (p), s30/s31 (return address), s36/s37 (call)
+
+
+def gen_sqr():
+    """The squaring's straight-line body: v[0:11] <- v[0:11]^2 / 2^384 mod p, canonical, for an operand < 2^382."""
+    Aa = lambda j: "v%d" % j
+    Dd = lambda k: "v%d" % (12 + k)
+    Ee = lambda j: "v%d" % (12 + j % 2)  # E_(j+1), read by column 2j + 1 only
+    Mm = lambda j: "v%d" % (24 + j)
+    Bb = lambda j: "v%d" % (12 + j)
+    out = []
+    w = out.append
+    _p_sgprs(w)
+    for k in range(2, N32):
+        w("v_alignbit_b32 %s, %s, %s, 31" % (Dd(k), Aa(k), Aa(k - 1)))
+
+    def col_terms(i):
+        if i % 2 == 0 and i + 1 <= 2 * N32 - 2:
+            w("v_lshlrev_b32 %s, 1, %s" % (Ee(i // 2), Aa(i // 2 + 1)))
+        body = []
+        for j in range(max(0, i - N32 + 1), i // 2 + 1):
+            k = i - j
+            bx = TOP_BOUND if j == N32 - 1 else LIMB_MAX
+            if k == j:
+                body.append((Aa(j), Aa(j), bx * bx))
+            elif k == j + 1:
+                body.append((Aa(j), Ee(j), bx * LIMB_MAX))
+            else:
+                body.append((Aa(j), Dd(k), bx * ((2 * TOP_BOUND + 1) if k == N32 - 1 else LIMB_MAX)))
+        return body
+
+    _comba(w, None, Mm, Aa, 36, True, col_terms)
+    _load_p(w, Mm)
+    w("v_sub_co_u32_e32 v12, vcc, v0, v24")
+    for j in range(1, N32):
+        w("v_subb_co_u32_e32 %s, vcc, %s, %s, vcc" % (Bb(j), Aa(j), Mm(j)))
+    for j in range(N32):
+        w("v_cndmask_b32_e64 %s, %s, %s, vcc" % (Aa(j), Bb(j), Aa(j)))
+    return out
+
+
+def gen_sqr_routine():
+    """The whole squaring routine as emitted, labels included: two entries around one copy of gen_sqr().
+    bls_fp_sqr_rt squares once; bls_fp_sqr_run_rt squares n >= 1 times without returning, n in SQR_RUN_SGPR
+    (clobbered, as is scc).  The value is canonical after every squaring, so a run equals n calls bit for bit; per
+    squaring it saves the call sequence (s_getpc, s_add, s_addc, s_swappc, s_setpc) and the operand moves against
+    two scalar instructions of loop control."""
+    c = SQR_RUN_SGPR
+    return (["bls_fp_sqr_rt:", "s_mov_b32 %s, 1" % c, "bls_fp_sqr_run_rt:", "s_sub_u32 %s, %s, 1" % (c, c),
+             "bls_fp_sqr_loop:"] + gen_sqr() +
+            ["s_sub_u32 %s, %s, 1" % (c, c), "s_cbranch_scc0 bls_fp_sqr_loop", "s_setpc_b64 s[30:31]"])
 
 
 # ---------------------------------------------------------------- Fp2 product as two sums of products
@@ -797,12 +865,17 @@ class DroppedCarry(AssertionError):
     pass
 
 
-def emulate(body, a, b, regs=None, strict=True):
+def emulate(body, a, b, regs=None, strict=True, entry=None, sregs=None):
     """Interprets the instruction subset used above (one lane); a, b: 12 x 32-bit limbs.
     Returns the 12 output limbs (v0..v11).  With regs (a dict VGPR number -> value, updated in place)
     the register file starts from regs instead of a in v0.. and b in v12..  strict: a v_mad_u64_u32 whose
-    carry-out is set must be followed by the v_addc that catches it (carry elision, _comba), else DroppedCarry."""
+    carry-out is set must be followed by the v_addc that catches it (carry elision, _comba), else DroppedCarry.
+    A stream with labels (gen_sqr_routine) starts at the label `entry`, with the SGPRs of `sregs` set, follows
+    s_cbranch_scc0 and ends at s_setpc_b64."""
     v, s = ({}, {}) if regs is None else (regs, {})
+    s.update(sregs or {})
+    labels = {x[:-1]: k for k, x in enumerate(body) if x.endswith(":")}
+    pc = 0 if entry is None else labels[entry]
     for j in range(N32):  # the callers' SGPRs (P_SGPR): p and -p^-1 mod 2^32
         s["s%d" % (16 + j)] = PL32[j]
     s["s28"] = (-pow(P, -1, 1 << 32)) % (1 << 32)
@@ -840,7 +913,11 @@ def emulate(body, a, b, regs=None, strict=True):
         else:
             v[int(x[1:])] = val & M32
 
-    for ins in body:
+    while pc < len(body):
+        ins = body[pc]
+        pc += 1
+        if ins.endswith(":"):
+            continue
         op, rest = ins.split(" ", 1)
         o = [t.strip() for t in rest.split(",")]
         if pending[0] is not None:
@@ -849,6 +926,16 @@ def emulate(body, a, b, regs=None, strict=True):
             pending[0] = None
         if op == "s_mov_b32":
             s[o[0]] = rd(o[1])
+        elif op == "s_sub_u32":
+            r = rd(o[1]) - rd(o[2])
+            s[o[0]], s["scc"] = r & M32, 1 if r < 0 else 0
+        elif op == "s_cbranch_scc0":
+            if not s["scc"]:
+                pc = labels[o[0]]
+        elif op == "s_setpc_b64":
+            break
+        elif op == "v_lshlrev_b32":
+            wr(o[0], rd(o[2]) << rd(o[1]))
         elif op in ("v_mov_b32", "v_mov_b64"):
             wr(o[0], rd(o[1]))
         elif op == "v_mad_u64_u32":
@@ -941,7 +1028,7 @@ def body_text(square=False, chains=2, sched=True, pool=("vcc",)):
     return [x.text for x in order], cyc
 
 
-def emit_header(path, bodies, extra=()):
+def emit_header(path, bodies, extra=(), routines=()):
     lines = ["// GENERATED by charon_amd/tools/gen_fp_asm.py -- do not edit.",
              "// gfx950 Montgomery product r = a*b/2^384 mod p (canonical), product scanning, %d instructions."
              % len(bodies[0][1]),
@@ -953,9 +1040,17 @@ def emit_header(path, bodies, extra=()):
             sep = "\\n\\t" if k + 1 < len(body) else ""
             lines.append('  "%s%s" \\' % (ins, sep))
         lines.append("")
+    for name, body in routines:  # whole routines: label lines stand alone, instructions are tab-indented
+        lines.append("// %s: %d instructions, labels included" % (name, sum(not x.endswith(":") for x in body)))
+        lines.append("#define %s \\" % name)
+        for ins in body:
+            lines.append('  "%s\\n" \\' % (ins if ins.endswith(":") else "\\t" + ins))
+        lines.append("")
     sg = "" if P_SGPR else ", " + ", ".join('"s%d"' % r for r in range(16, 29))  # s16-s28: inputs with P_SGPR
     clob = ", ".join('"v%d"' % r for r in range(24, 40)) + ', "vcc"' + sg
     lines.append("#define BLS_FP_MUL_ASM_CLOBBERS %s" % clob)
+    clobs = ", ".join('"v%d"' % r for r in range(12, 40)) + ', "vcc"' + sg
+    lines.append("#define BLS_FP_SQR_ASM_CLOBBERS %s" % clobs)
     clob2 = ", ".join('"v%d"' % r for r in list(range(48, 52)) + list(range(76, 88))) + ', "vcc"' + sg
     lines.append("#define BLS_FP2_MUL_ASM_CLOBBERS %s" % clob2)
     clob3 = ", ".join('"v%d"' % r for r in range(48, 64)) + ', "vcc"' + sg
@@ -999,6 +1094,7 @@ def emit_lazy_header(path):
 def main(lazy=False):
     mul = gen_mul()
     check(mul, mont=1 << 384, canonical=True)
+    check(gen_sqr(), square=True, mont=1 << 384, canonical=True)
     pkg = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.path.join(pkg, "csrc", "fp_asm_gfx950.h")
     fp2 = gen_fp2_mul()
@@ -1007,7 +1103,9 @@ def main(lazy=False):
                        ("BLS_FP2_MUL_HALF_ASM_BODY", gen_fp2_mul_half()),
                        ("BLS_FP2_SQR_HALF_ASM_BODY", gen_fp2_sqr_half())],
                 extra=[("BLS_FP_ADD_ASM", gen_add()), ("BLS_FP_SUB_ASM", gen_sub()), ("BLS_FP_NEG_ASM", gen_sub(neg=True)),
-                       ("BLS_FP_ADD_LAZY_ASM", gen_add_lazy()), ("BLS_FP_SUB_LAZY_ASM", gen_sub_lazy())])
+                       ("BLS_FP_ADD_LAZY_ASM", gen_add_lazy()), ("BLS_FP_SUB_LAZY_ASM", gen_sub_lazy())],
+                routines=[("BLS_FP_SQR_ASM_ROUTINE", gen_sqr_routine())])
+    print("squaring: %d instructions per squaring, %d with loop control" % (len(gen_sqr()), len(gen_sqr()) + 2))
     print("wrote %s: %d instructions" % (path, len(mul)))
     if lazy:
         lpath = os.path.join(pkg, "tools", "fp_asm_lazy_gfx950.h")
