@@ -101,6 +101,34 @@ inline bool hcache_assign(HCacheState& hc, const uint8_t* msgs, const uint64_t* 
   return true;
 }
 
+// The read-only lookup of a call that consumes a root last (the keyed FastAggregateVerify, hipbls.hip fav_keys_host):
+// src[m] = kHCacheColumn | column for a message the cache holds, else m itself, the message's column in a table of the
+// call's own, and `miss` lists those messages (the ones the call hashes).  Hits and misses count per distinct message;
+// nothing is inserted or evicted and the ring keeps its place, so there is nothing to undo when the call fails.
+// Bypassed exactly where hcache_assign bypasses (disabled, or more messages than columns): every message is the call's
+// own and nothing counts.  Returns whether any message was found.
+constexpr uint32_t kHCacheColumn = 0x80000000u;
+inline bool hcache_read(HCacheState& hc, const uint8_t* msgs, const uint64_t* offs, uint64_t n_msgs,
+                        std::vector<uint32_t>& src, std::vector<uint32_t>& miss) {
+  const bool lookup = hc.cap != 0 && n_msgs <= hc.cap;
+  src.assign(n_msgs, 0);
+  miss.clear();
+  bool any = false;
+  for (uint64_t m = 0; m < n_msgs; ++m) {
+    auto it = lookup ? hc.map.find(std::string((const char*)msgs + offs[m], offs[m + 1] - offs[m])) : hc.map.end();
+    if (it != hc.map.end()) {
+      src[m] = kHCacheColumn | (uint32_t)it->second;
+      hc.hits += 1;
+      any = true;
+    } else {
+      src[m] = (uint32_t)m;
+      miss.push_back((uint32_t)m);
+      if (lookup) hc.misses += 1;
+    }
+  }
+  return any;
+}
+
 // The error path of a call whose launch failed after hcache_assign: its misses' columns were never written, so their
 // entries leave the map (a later call hashes those roots again instead of reading an unwritten column as H(m)).  The
 // entries the misses evicted stay gone; the ring keeps its place.

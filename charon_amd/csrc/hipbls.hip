@@ -42,6 +42,7 @@
 
 #include <sys/random.h>
 
+#include "fav_split.h"
 #include "hcache_assign.h"
 #include "kernels.h"
 #include "ranges.h"
@@ -103,6 +104,11 @@ __global__ void k_tv_pair_lq16(const uint32_t* pts, const int32_t* pstat, const 
 namespace bls_hexw {
 __global__ void k_fav_pair_lq16(const uint32_t* pts, const int32_t* kcode, uint64_t nkeys, const uint64_t* goff,
                                 const uint32_t* ws, uint64_t G, int32_t* status);
+__global__ void k_fav_pair_lq16_keys(const uint32_t* key_idx, uint64_t T, const int32_t* tcode, const uint32_t* tab,
+                                     const uint64_t* poff, const uint32_t* parts, const int32_t* pflags,
+                                     uint64_t n_slices, const uint64_t* goff, const uint32_t* hcol,
+                                     const uint32_t* Hcache, uint64_t cstride, const uint32_t* Hc, uint64_t hstride,
+                                     const uint32_t* ws, uint64_t G, int32_t* status);
 }  // namespace bls_hexw
 namespace bls_fp2p {
 // LDS the S-factor workgroup reserves at launch and never touches: the chunk kernel's 36 KiB per workgroup (four per
@@ -243,6 +249,10 @@ struct Context {
   DevBuf r_pk, r_sig, r_h, r_win, r_midx, r_list, r_cnt, r_slot, r_mlist;  // RLC BatchVerify workspaces
   DevBuf t_code, t_tab, b_kidx;                                            // resident pubshare table + key indices
   DevBuf f_ws;  // FastAggregateVerify on the octet / sixteen-lane layouts: per-group H(m), signature, codes
+  // FastAggregateVerify with keys by table index (launch_fav_keys): the call's own H(m) table; the host call's H(m)
+  // column per group and miss list (used under the lock up to the call's stream sync)
+  DevBuf fk_h, fk_hcol, fk_mlist;
+  DevBuf fk_slices, fk_poff, fk_parts, fk_pflags;  // its split key sum: slice plan, partial sums and their flags
   DevBuf v_ws;                                                             // lane-pair Verify points (SoA)
   // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
   // the call's own H(m) table and its prep + check workspace; used under the lock up to the call's stream sync
@@ -466,6 +476,7 @@ const KernelRef kKernels[] = {
     KREF8(k_tv_prep8), KREF8(k_tagg_sum8), KREF16(k_tv_pair_lq16),
     KREF(k_tv_phase_a_keys), KREF(k_tv_join_keys), KREF(k_tv_gather_keys), KREF8(k_tv_prep8_keys),
     KREF(k_verify_gather_keys), KREF8(k_verify_prep8_keys), KREF8(k_hcache_fill8),
+    KREF(k_fav_batch_keys), KREF16W(k_fav_pair_lq16_keys), KREF(k_fav_sum_keys),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -1893,6 +1904,100 @@ int launch_fav(Context& c, const uint8_t* d_pks, uint64_t nkeys, const uint64_t*
   return ws_end(c, s);
 }
 
+// FastAggregateVerify with keys by table index (hipbls_verify_aggregate_batch_keys[_device]): key k of
+// the call is table[d_kidx[k]], so nothing is decompressed or subgroup-tested, and d_msgs / d_moffs hold n_msgs messages
+// of which the n_hash in d_mlist (nullptr: 0 .. n_hash - 1) are hashed into the call's own table fk_h (stride n_msgs).
+// Group g reads its H(m) where it lies (fav_keys.h fav_h_cols): d_hcol[g] names a column of the H(m) cache or of fk_h;
+// without d_hcol (the _device call) group g's message is message g.  Routes as launch_fav:
+//   * lone (use_fav_hex): signatures and the missing hashes on octets (verify_lat.hip k_verify_prep8_keys, whose
+//     workspace layout is k_fav_prep8's: timed "fav_prep8_keys"), then k_fav_pair_lq16_keys ("fav_lq16_keys");
+//   * throughput: the missing hashes on one lane each (k_rlc_hash), then k_fav_batch_keys ("fav_keys").
+// reads_cache: some column is the cache's, read after any RLC call that may still be filling it (ws_done_rlc); the host
+// call drains its stream before it releases the context lock, so no later writer meets these reads.
+// Split key sum (the host call only: the slice plan comes from the key offsets, fav_split.h): with n_slices > 0 the
+// groups that own slices (d_poff) get them folded first, one workgroup per slice (k_fav_sum_keys, "fav_sum_keys"), and
+// the check kernel adds their partials.  A group above kFavSumSplit keys is cut; HIPBLS_FAV_SUM_SPLIT, read at init,
+// overrides the threshold, 0 turns the split off.  The threshold is the measured break-even (profiles/r13, the lock's
+// one group of 40,000 keys): the check's own walk costs 9.2 ms for 625 additions per lane, 14.8 us per 64 keys, and
+// the slice sum 0.38 ms as a launch, so a group pays for its slice sum from about 1,640 keys on; 2,048 is the next
+// power of two, and the sync committee's 512 keys (0.12 ms of walk) stay whole.
+struct FavKeys {
+  const uint32_t *d_kidx, *d_hcol, *d_mlist;
+  uint64_t n_hash, n_msgs;
+  bool reads_cache;
+  const uint64_t *d_slices, *d_poff;
+  uint64_t n_slices;
+};
+constexpr uint64_t kFavSumSplit = 2048;
+uint64_t initial_fav_sum_split() {
+  const char* e = getenv("HIPBLS_FAV_SUM_SPLIT");
+  if (!e || !*e) return kFavSumSplit;
+  char* end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  return end && *end == 0 ? (uint64_t)v : kFavSumSplit;
+}
+const uint64_t g_fav_sum_split = initial_fav_sum_split();
+int launch_fav_keys(Context& c, const FavKeys& K, const uint64_t* d_goff, uint64_t n_groups, const uint8_t* d_sigs,
+                    const uint8_t* d_msgs, const uint64_t* d_moffs, int32_t* d_status, hipStream_t s) {
+  if (n_groups == 0) return HIPBLS_OK;
+  HIP_TRY(c.fk_h.ensure((K.n_msgs ? K.n_msgs : 1) * 48 * 4));
+  const bool hex = use_fav_hex(n_groups);
+  if (hex) HIP_TRY(c.f_ws.ensure(n_groups * 122 * 4));
+  int rc = ws_begin(c, s);
+  if (rc) return rc;
+  if (K.reads_cache) HIP_TRY(hipStreamWaitEvent(s, c.ws_done_rlc, 0));
+  const uint64_t T = c.t_size, cstride = c.hcache.cap;
+  const int32_t* tcode = (const int32_t*)c.t_code.p;
+  const uint32_t* tab = (const uint32_t*)c.t_tab.p;
+  const uint32_t* Hcache = (const uint32_t*)c.hcache.table.p;
+  uint32_t* Hc = (uint32_t*)c.fk_h.p;
+  const uint64_t* poff = nullptr;
+  const uint32_t* parts = nullptr;
+  const int32_t* pflags = nullptr;
+  if (K.n_slices) {
+    HIP_TRY(c.fk_parts.ensure(K.n_slices * 36 * 4));
+    HIP_TRY(c.fk_pflags.ensure(K.n_slices * 2 * 4));
+    poff = K.d_poff;
+    parts = (const uint32_t*)c.fk_parts.p;
+    pflags = (const int32_t*)c.fk_pflags.p;
+    rc = timed(c, "fav_sum_keys", s, [&] {
+      hipLaunchKernelGGL(k_fav_sum_keys, dim3((unsigned)K.n_slices), dim3(kFavSumBlock), 0, s, K.d_kidx, T, tcode, tab,
+                         K.d_slices, K.n_slices, (uint32_t*)c.fk_parts.p, (int32_t*)c.fk_pflags.p);
+    });
+    if (rc) return rc;
+  }
+  if (hex) {
+    // the kernel derives the same role boundaries from n_hash and n_groups
+    const uint64_t nbh = (8 * K.n_hash + kBlock - 1) / kBlock, nbs = (8 * n_groups + kBlock - 1) / kBlock;
+    rc = timed(c, "fav_prep8_keys", s, [&] {
+      hipLaunchKernelGGL(bls_fp2p::k_verify_prep8_keys, dim3((unsigned)(nbh + nbs)), dim3(kBlock), 0, s, d_msgs,
+                         d_moffs, K.d_mlist, K.n_hash, (const uint32_t*)nullptr, Hc, K.n_msgs, d_sigs, n_groups,
+                         (uint32_t*)c.f_ws.p);
+    });
+    if (rc) return rc;
+    rc = timed(c, "fav_lq16_keys", s, [&] {
+      hipLaunchKernelGGL(bls_hexw::k_fav_pair_lq16_keys, dim3((unsigned)n_groups), dim3(kBlock), 0, s, K.d_kidx, T,
+                         tcode, tab, poff, parts, pflags, K.n_slices, d_goff, K.d_hcol, Hcache, cstride, (const uint32_t*)Hc, K.n_msgs,
+                         (const uint32_t*)c.f_ws.p, n_groups, d_status);
+    });
+    if (rc) return rc;
+    return ws_end(c, s);
+  }
+  if (K.n_hash) {
+    rc = timed(c, "rlc_hash", s, [&] {
+      hipLaunchKernelGGL(k_rlc_hash, dim3((unsigned)grid_for(K.n_hash)), dim3(kBlock), 0, s, d_msgs, d_moffs, K.n_hash,
+                         K.d_mlist, Hc, K.n_msgs, (const uint32_t*)nullptr);
+    });
+    if (rc) return rc;
+  }
+  rc = timed(c, "fav_keys", s, [&] {
+    hipLaunchKernelGGL(k_fav_batch_keys, dim3((unsigned)n_groups), dim3(kFavBlock), 0, s, K.d_kidx, T, tcode, tab,
+                       poff, parts, pflags, K.n_slices, d_goff, d_sigs, K.d_hcol, Hcache, cstride, (const uint32_t*)Hc, K.n_msgs, d_status);
+  });
+  if (rc) return rc;
+  return ws_end(c, s);
+}
+
 // Aggregate: decode in parallel, per-workgroup partial sums, one final workgroup (kernels.h).
 int launch_aggregate(Context& c, const uint8_t* d_sigs, uint64_t n, uint8_t* d_out, int32_t* d_status, hipStream_t s) {
   const uint64_t per_wg = 8 * (uint64_t)kSumBlock;  // points folded per lane before the tree
@@ -2783,6 +2888,66 @@ int fav_host(Context& c, const uint8_t* pks, const uint64_t* koffs, uint64_t n_g
   return HIPBLS_OK;
 }
 
+// The keyed FastAggregateVerify from host buffers, on one context (lock held): the groups' messages are folded to the
+// distinct ones, each of which is looked up in the context's H(m) cache -- read only, as the keyed sigagg
+// (tagg_verify_host): FastAggregateVerify is the last consumer of a root, so it neither inserts nor evicts, and needs
+// no undo path -- a hit counts per distinct message and is read from its column, a miss is hashed once into the call's
+// own table, also with the cache off or smaller than the call.  Returns after the stream has drained.
+int fav_keys_host(Context& c, const uint32_t* key_idx, const uint64_t* koffs, uint64_t n_groups, const uint8_t* sigs,
+                  const uint8_t* msgs, const uint64_t* moffs, int32_t* status) {
+  const uint64_t nkeys = koffs[n_groups];
+  for (uint64_t k = 0; k < nkeys; ++k)
+    if (key_idx[k] >= c.t_size) return arg_err("key index outside the pubshare table");
+  std::vector<uint8_t> umsg;
+  std::vector<uint64_t> uoff;
+  std::vector<uint32_t> mid, mlist;
+  distinct_messages(msgs, moffs, n_groups, umsg, uoff, mid);
+  const uint64_t n_msgs = uoff.size() - 1, msg_total = uoff[n_msgs];
+  static_assert(kHCacheColumn == kFavHCached, "hcache_read's column bit is the one fav_h_cols reads");
+  std::vector<uint32_t> src, hcol(n_groups);
+  const bool any_hit = hcache_read(c.hcache, umsg.data(), uoff.data(), n_msgs, src, mlist);
+  for (uint64_t g = 0; g < n_groups; ++g) hcol[g] = src[mid[g]];
+  FavSplitPlan plan;
+  const bool split = fav_split_plan(koffs, n_groups, g_fav_sum_split, plan);
+  if (split && plan.n_slices() > 0x7fffffffull) return arg_err("too many key slices");
+  const hipStream_t s = c.stream;
+  // every exit drains the stream: no queued copy may still read the vectors above
+  struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{s};
+  HIP_TRY(c.b_kidx.ensure((nkeys ? nkeys : 1) * 4));
+  HIP_TRY(c.b_ids.ensure((n_groups + 1) * 8));
+  HIP_TRY(c.b_sig.ensure(n_groups * 96));
+  HIP_TRY(c.b_msg.ensure(msg_total ? msg_total : 1));
+  HIP_TRY(c.b_off.ensure((n_msgs + 1) * 8));
+  HIP_TRY(c.b_st.ensure(n_groups * 4));
+  HIP_TRY(c.fk_hcol.ensure(n_groups * 4));
+  HIP_TRY(c.fk_mlist.ensure((mlist.size() ? mlist.size() : 1) * 4));
+  if (nkeys) HIP_TRY(hipMemcpyAsync(c.b_kidx.p, key_idx, nkeys * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.b_ids.p, koffs, (n_groups + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.b_sig.p, sigs, n_groups * 96, hipMemcpyHostToDevice, s));
+  if (msg_total) HIP_TRY(hipMemcpyAsync(c.b_msg.p, umsg.data(), msg_total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.b_off.p, uoff.data(), (n_msgs + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c.fk_hcol.p, hcol.data(), n_groups * 4, hipMemcpyHostToDevice, s));
+  if (mlist.size()) HIP_TRY(hipMemcpyAsync(c.fk_mlist.p, mlist.data(), mlist.size() * 4, hipMemcpyHostToDevice, s));
+  if (split) {
+    HIP_TRY(c.fk_slices.ensure(plan.slices.size() * 8));
+    HIP_TRY(c.fk_poff.ensure(plan.poff.size() * 8));
+    HIP_TRY(hipMemcpyAsync(c.fk_slices.p, plan.slices.data(), plan.slices.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c.fk_poff.p, plan.poff.data(), plan.poff.size() * 8, hipMemcpyHostToDevice, s));
+  }
+  const FavKeys K{(const uint32_t*)c.b_kidx.p, (const uint32_t*)c.fk_hcol.p, (const uint32_t*)c.fk_mlist.p,
+                  mlist.size(), n_msgs, any_hit, (const uint64_t*)c.fk_slices.p, (const uint64_t*)c.fk_poff.p,
+                  split ? plan.n_slices() : 0};
+  int rc = launch_fav_keys(c, K, (const uint64_t*)c.b_ids.p, n_groups, (const uint8_t*)c.b_sig.p,
+                           (const uint8_t*)c.b_msg.p, (const uint64_t*)c.b_off.p, (int32_t*)c.b_st.p, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_groups * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return HIPBLS_OK;
+}
+
 int aggregate_host(Context& c, const uint8_t* sigs, uint64_t n, uint8_t* out_sig, int32_t* status) {
   HIP_TRY(c.b_sig.ensure((n ? n : 1) * 96));
   HIP_TRY(c.b_out.ensure(96));
@@ -3380,6 +3545,52 @@ int hipbls_verify_aggregate_batch_device(const uint8_t* d_pks, uint64_t nkeys, c
   ON_STREAM(c, stream, s);
   return launch_fav(c, d_pks, nkeys, d_key_offsets, n_groups, d_sigs, d_msgs, d_msg_offsets, d_status,
                     s);
+}
+
+// Whole groups per device, as the wire-format call; every context holds the table and looks the range's messages up
+// in its own H(m) cache.
+int hipbls_verify_aggregate_batch_keys(const uint32_t* key_idx, const uint64_t* key_offsets, uint64_t n_groups,
+                                       const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                       int32_t* status) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!key_offsets || !sigs || !msg_offsets || !status || mul_overflows(n_groups, 122 * 4))
+    return arg_err("bad arguments");
+  if (!groups_ok(key_offsets, n_groups)) return arg_err("bad key offsets");
+  if (!offsets_ok(msg_offsets, n_groups)) return arg_err("bad message offsets");
+  const uint64_t nkeys = key_offsets[n_groups], msg_total = msg_offsets[n_groups];
+  if ((nkeys && !key_idx) || (msg_total && !msgs) || mul_overflows(nkeys, 4)) return arg_err("bad arguments");
+  ENSURE_INIT();
+  uint64_t T = 0;
+  {
+    std::lock_guard<std::mutex> lk(ctx(0).mu);
+    T = ctx(0).t_size;
+  }
+  for (uint64_t k = 0; k < nkeys; ++k)
+    if (key_idx[k] >= T) return arg_err("key index outside the pubshare table");
+  return run_ranges(plan_ranges(n_groups, parts_for(n_groups, kSplitFav), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      std::vector<uint64_t> tk, tm;
+                      return fav_keys_host(c, key_idx ? key_idx + key_offsets[lo] : key_idx,
+                                           rebase(key_offsets, lo, hi, tk), hi - lo, sigs + 96 * lo,
+                                           msgs ? msgs + msg_offsets[lo] : msgs, rebase(msg_offsets, lo, hi, tm),
+                                           status + lo);
+                    });
+}
+
+int hipbls_verify_aggregate_batch_keys_device(const uint32_t* d_key_idx, uint64_t nkeys, const uint64_t* d_key_offsets,
+                                              uint64_t n_groups, const uint8_t* d_sigs, const uint8_t* d_msgs,
+                                              const uint64_t* d_msg_offsets, int32_t* d_status, void* stream) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!d_key_offsets || !d_sigs || !d_msg_offsets || !d_status || (nkeys && !d_key_idx) ||
+      mul_overflows(n_groups, 122 * 4))
+    return arg_err("bad arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  // the host never sees the messages: each group's message is hashed into the call's own table, the cache is untouched
+  const FavKeys K{d_key_idx, nullptr, nullptr, n_groups, n_groups, false, nullptr, nullptr, 0};
+  return launch_fav_keys(c, K, d_key_offsets, n_groups, d_sigs, d_msgs, d_msg_offsets, d_status, s);
 }
 
 int hipbls_verify_aggregate(const uint8_t* pks, uint64_t n, const uint8_t* sig, const uint8_t* msg, uint64_t msg_len,

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "fav_keys.h"
 #include "lg2.h"
 #include "ops.h"
 #include "rlc.h"
@@ -641,16 +642,26 @@ __global__ void __launch_bounds__(kBlock) k_g1_decode(const uint8_t* __restrict_
 // Status order follows the reference: signature decode error, then key decode error, then
 // "signature verification failed" (also for an empty key list, an infinity key or signature).
 constexpr int kFavBlock = 128;
-__global__ void __launch_bounds__(kFavBlock) k_fav_batch(const uint32_t* __restrict__ pts,
-                                                         const int32_t* __restrict__ code, uint64_t nkeys,
-                                                         const uint64_t* __restrict__ goff,
-                                                         const uint8_t* __restrict__ sigs,
-                                                         const uint8_t* __restrict__ msgs,
-                                                         const uint64_t* __restrict__ moffs,
-                                                         int32_t* __restrict__ status) {
-  __shared__ uint32_t red[64 * 36];
-  __shared__ uint32_t sh_sig[48], sh_hm[48];
-  __shared__ int sh_ds, sh_bad, sh_inf;
+// The wire-format call's H(m): wave 1's lane hashes group g's message itself.
+struct fav_h_hash {
+  const uint8_t* msgs;
+  const uint64_t* moffs;
+  __device__ __forceinline__ void load(g2a& hm, uint64_t g) const {
+    g2j hj;
+    const uint64_t o0 = moffs[g], o1 = moffs[g + 1];
+    hash_to_g2(hj, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43);
+    jac_to_aff(hm, hj);
+  }
+};
+
+// The body, shared by k_fav_batch and its twin with keys by table index (fav_keys.h has the loaders).  Keys: where key
+// k's DEC_* code and affine point come from; HSrc: what wave 1's lane does for H(m) once the signature has decoded.  A
+// key index outside the table (fav_tab_keys only, the _device call) sets bit 1 of sh_bad and makes the group ERR_ARG.
+template <class Keys, class HSrc>
+__device__ __forceinline__ void fav_batch_body(const Keys& keys, const HSrc& hsrc, const uint64_t* __restrict__ goff,
+                                               const uint8_t* __restrict__ sigs, int32_t* __restrict__ status,
+                                               uint32_t* red, uint32_t* sh_sig, uint32_t* sh_hm, int& sh_ds,
+                                               int& sh_bad, int& sh_inf) {
   const uint64_t g = blockIdx.x;
   const uint64_t k0 = goff[g], k1 = goff[g + 1];
   const int tid = threadIdx.x;
@@ -663,19 +674,8 @@ __global__ void __launch_bounds__(kFavBlock) k_fav_batch(const uint32_t* __restr
     g1j acc;
     jac_set_inf(acc);
     int bad = 0, inf = 0;
-    for (uint64_t k = k0 + tid; k < k1; k += 64) {
-      const int c = code[k];
-      if (c == DEC_BAD) {
-        bad = 1;
-      } else if (c == DEC_INF) {
-        inf = 1;
-      } else {
-        g1a a;
-        soa_load<24>(&a.x.v[0], pts, nkeys, k);
-        jac_add_aff(acc, acc, a);
-      }
-    }
-    if (bad) atomicOr(&sh_bad, 1);
+    fav_fold_group(acc, bad, inf, keys, g, k0, k1, tid);
+    if (bad) atomicOr(&sh_bad, bad);
     if (inf) atomicOr(&sh_inf, 1);
     for (int w = 0; w < 36; ++w) red[w * 64 + tid] = (&acc.x.v[0])[w];
   } else if (tid == 64) {
@@ -684,10 +684,7 @@ __global__ void __launch_bounds__(kFavBlock) k_fav_batch(const uint32_t* __restr
     sh_ds = ds;
     g2a hm;
     if (ds == DEC_OK) {
-      g2j hj;
-      const uint64_t o0 = moffs[g], o1 = moffs[g + 1];
-      hash_to_g2(hj, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43);
-      jac_to_aff(hm, hj);
+      hsrc.load(hm, g);
     } else {
       fp2_set_zero(sg.x);
       fp2_set_zero(sg.y);
@@ -699,24 +696,15 @@ __global__ void __launch_bounds__(kFavBlock) k_fav_batch(const uint32_t* __restr
     }
   }
   __syncthreads();
-  for (int half = 32; half >= 1; half >>= 1) {  // every thread reaches every barrier
-    if (tid < half) {
-      g1j x, y;
-      for (int w = 0; w < 36; ++w) {
-        (&x.x.v[0])[w] = red[w * 64 + tid];
-        (&y.x.v[0])[w] = red[w * 64 + tid + half];
-      }
-      jac_add(x, x, y);
-      for (int w = 0; w < 36; ++w) red[w * 64 + tid] = (&x.x.v[0])[w];
-    }
-    __syncthreads();
-  }
+  fav_tree(red, tid);
   // lanes 0 and 1 finish as a pair (lg2.h): e(pk, H(m)) on lane 0 and e(-g1, sig) on lane 1, split final
   // exponentiation; every branch below depends on shared values only, so the pair stays together
   if (tid >= 2) return;
   const uint32_t lm = tid ? ~0u : 0u;
   int st;
-  if (sh_ds == DEC_BAD) {
+  if (Keys::kIndexed && (sh_bad & 2)) {
+    st = HIPBLS_ERR_ARG;
+  } else if (sh_ds == DEC_BAD) {
     st = HIPBLS_ERR_SIGNATURE;
   } else if (sh_bad) {
     st = HIPBLS_ERR_PUBKEY;
@@ -749,6 +737,79 @@ __global__ void __launch_bounds__(kFavBlock) k_fav_batch(const uint32_t* __restr
     }
   }
   if (tid == 0) status[g] = st;
+}
+
+__global__ void __launch_bounds__(kFavBlock) k_fav_batch(const uint32_t* __restrict__ pts,
+                                                         const int32_t* __restrict__ code, uint64_t nkeys,
+                                                         const uint64_t* __restrict__ goff,
+                                                         const uint8_t* __restrict__ sigs,
+                                                         const uint8_t* __restrict__ msgs,
+                                                         const uint64_t* __restrict__ moffs,
+                                                         int32_t* __restrict__ status) {
+  __shared__ uint32_t red[64 * 36];
+  __shared__ uint32_t sh_sig[48], sh_hm[48];
+  __shared__ int sh_ds, sh_bad, sh_inf;
+  fav_batch_body(fav_wire_keys{pts, code, nkeys}, fav_h_hash{msgs, moffs}, goff, sigs, status, red, sh_sig, sh_hm,
+                 sh_ds, sh_bad, sh_inf);
+}
+
+// k_fav_batch for the call with keys by table index (hipbls_verify_aggregate_batch_keys[_device]; hipbls.hip
+// launch_fav_keys): key k is table[key_idx[k]], no decode and no subgroup test, and wave 1's lane only decodes the
+// signature and fetches the group's H(m) (fav_keys.h fav_h_cols), which k_rlc_hash or an earlier call computed.  A
+// group that the host cut into slices adds its slices' partial sums (k_fav_sum_keys) instead of walking its keys.
+__global__ void __launch_bounds__(kFavBlock) k_fav_batch_keys(
+    const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+    const uint32_t* __restrict__ tab, const uint64_t* __restrict__ poff, const uint32_t* __restrict__ parts,
+    const int32_t* __restrict__ pflags, uint64_t n_slices, const uint64_t* __restrict__ goff,
+    const uint8_t* __restrict__ sigs, const uint32_t* __restrict__ hcol, const uint32_t* __restrict__ Hcache,
+    uint64_t cstride, const uint32_t* __restrict__ Hc, uint64_t hstride, int32_t* __restrict__ status) {
+  __shared__ uint32_t red[64 * 36];
+  __shared__ uint32_t sh_sig[48], sh_hm[48];
+  __shared__ int sh_ds, sh_bad, sh_inf;
+  fav_batch_body(fav_tab_keys{key_idx, T, tcode, tab, poff, parts, pflags, n_slices},
+                 fav_h_cols{hcol, Hcache, cstride, Hc, hstride}, goff, sigs, status, red, sh_sig, sh_hm, sh_ds, sh_bad,
+                 sh_inf);
+}
+
+// The split key sum of the keyed FastAggregateVerify (hipbls.hip fav_keys_host; the slice plan is fav_split.h's): a
+// group of very many keys -- the cluster lock's aggregate over every pubshare -- would have one workgroup walk all of
+// them, so the host cuts it into slices and workgroup s folds the keys [slices[2 s], slices[2 s + 1]) of slice s, as
+// the check kernels fold a whole group: strided mixed additions on 64 lanes, then the LDS tree.  Lane 0 writes the
+// slice's Jacobian partial (36 words, SoA over n_slices) and its bad and identity flags; the check kernel adds the
+// group's partials (fav_keys.h fav_fold_group).
+constexpr int kFavSumBlock = 64;
+__global__ void __launch_bounds__(kFavSumBlock) k_fav_sum_keys(const uint32_t* __restrict__ key_idx, uint64_t T,
+                                                               const int32_t* __restrict__ tcode,
+                                                               const uint32_t* __restrict__ tab,
+                                                               const uint64_t* __restrict__ slices, uint64_t n_slices,
+                                                               uint32_t* __restrict__ parts,
+                                                               int32_t* __restrict__ pflags) {
+  __shared__ uint32_t red[64 * 36];
+  __shared__ int sh_bad, sh_inf;
+  const uint64_t sl = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    sh_bad = 0;
+    sh_inf = 0;
+  }
+  __syncthreads();
+  {
+    g1j acc;
+    jac_set_inf(acc);
+    int bad = 0, inf = 0;
+    fav_fold(acc, bad, inf, fav_tab_keys{key_idx, T, tcode, tab, nullptr, nullptr, nullptr, 0}, slices[2 * sl],
+             slices[2 * sl + 1], tid);
+    if (bad) atomicOr(&sh_bad, bad);
+    if (inf) atomicOr(&sh_inf, 1);
+    for (int w = 0; w < 36; ++w) red[w * 64 + tid] = (&acc.x.v[0])[w];
+  }
+  __syncthreads();
+  fav_tree(red, tid);
+  if (tid < 36) parts[(uint64_t)tid * n_slices + sl] = red[tid * 64];
+  if (tid == 0) {
+    pflags[2 * sl] = sh_bad;
+    pflags[2 * sl + 1] = sh_inf;
+  }
 }
 
 // Aggregate (tbls/herumi.go:220-242): sum of n signatures in G2.  Stage 1 decodes every signature in parallel

@@ -25,6 +25,8 @@
 #include "lg2.h"
 #ifndef BLS_HEX_FAV_WIDE
 #include "tagg_lat.h"
+#else
+#include "fav_keys.h"
 #endif
 
 namespace bls {
@@ -133,13 +135,14 @@ __global__ void __launch_bounds__(kHexBlock) k_tv_pair_lq16(const uint32_t* __re
 #ifndef BLS_FAV_ATTR
 #define BLS_FAV_ATTR
 #endif
-__global__ void __launch_bounds__(kHexBlock) BLS_FAV_ATTR k_fav_pair_lq16(const uint32_t* __restrict__ pts,
-                                                             const int32_t* __restrict__ kcode, uint64_t nkeys,
-                                                             const uint64_t* __restrict__ goff,
-                                                             const uint32_t* __restrict__ ws, uint64_t G,
-                                                             int32_t* __restrict__ status) {
-  __shared__ uint32_t red[kHexBlock * 36];
-  __shared__ int sh_bad, sh_inf;
+// The body, shared by the wire-format kernel and its twin with keys by table index (fav_keys.h has the loaders).  Keys:
+// where key k's DEC_* code and affine point come from; HSrc: where group g's H(m) comes from.  A key index outside the
+// table (fav_tab_keys only, the _device call) sets bit 1 of sh_bad and makes the group ERR_ARG, whatever else it holds.
+template <class Keys, class HSrc>
+__device__ __forceinline__ void fav_pair_lq16_body(const Keys& keys, const HSrc& hsrc, const uint64_t* __restrict__ goff,
+                                                   const uint32_t* __restrict__ ws, uint64_t G,
+                                                   int32_t* __restrict__ status, uint32_t* red, int& sh_bad,
+                                                   int& sh_inf) {
   bls_race::init(nullptr, 0u);
   const uint64_t g = blockIdx.x;
   const int tid = threadIdx.x;
@@ -153,35 +156,14 @@ __global__ void __launch_bounds__(kHexBlock) BLS_FAV_ATTR k_fav_pair_lq16(const 
     g1j acc;
     jac_set_inf(acc);
     int bad = 0, inf = 0;
-    for (uint64_t k = k0 + tid; k < k1; k += kHexBlock) {
-      const int c = kcode[k];
-      if (c == DEC_BAD) {
-        bad = 1;
-      } else if (c == DEC_INF) {
-        inf = 1;
-      } else {
-        g1a a;
-        soa_load<24>(&a.x.v[0], pts, nkeys, k);
-        jac_add_aff(acc, acc, a);
-      }
-    }
-    if (bad) atomicOr(&sh_bad, 1);
+    fav_fold_group(acc, bad, inf, keys, g, k0, k1, tid);
+    if (bad) atomicOr(&sh_bad, bad);
     if (inf) atomicOr(&sh_inf, 1);
     for (int w = 0; w < 36; ++w) red[w * kHexBlock + tid] = (&acc.x.v[0])[w];
   }
   __syncthreads();
-  for (int half = kHexBlock / 2; half >= 1; half >>= 1) {  // every thread reaches every barrier
-    if (tid < half) {
-      g1j x, y;
-      for (int w = 0; w < 36; ++w) {
-        (&x.x.v[0])[w] = red[w * kHexBlock + tid];
-        (&y.x.v[0])[w] = red[w * kHexBlock + tid + half];
-      }
-      jac_add(x, x, y);
-      for (int w = 0; w < 36; ++w) red[w * kHexBlock + tid] = (&x.x.v[0])[w];
-    }
-    __syncthreads();
-  }
+  static_assert(kHexBlock == 64, "fav_keys.h folds and reduces over 64 lanes");
+  fav_tree(red, tid);
   if (tid >= 16) return;  // lanes 0-15: the check, every branch below on shared values only
   const int ds = ((const int32_t*)(ws + 120 * G))[2 * g + 1];
   g1j sum;
@@ -197,12 +179,14 @@ __global__ void __launch_bounds__(kHexBlock) BLS_FAV_ATTR k_fav_pair_lq16(const 
       pk.y = G1_NEG_GEN_Y;
     }
     g2a hm, sig;
-    soa_load<48>(&hm.x.c0.v[0], ws + 24 * G, G, g);
+    hsrc.load(hm, g);
     soa_load<48>(&sig.x.c0.v[0], ws + 72 * G, G, g);
     chk = lq4_verify(pk, hm, sig, tid & 3);
   }
   int st;
-  if (ds == DEC_BAD || chk == HIPBLS_ERR_SIGNATURE)
+  if (Keys::kIndexed && (sh_bad & 2))
+    st = HIPBLS_ERR_ARG;
+  else if (ds == DEC_BAD || chk == HIPBLS_ERR_SIGNATURE)
     st = HIPBLS_ERR_SIGNATURE;
   else if (sh_bad)
     st = HIPBLS_ERR_PUBKEY;
@@ -211,6 +195,41 @@ __global__ void __launch_bounds__(kHexBlock) BLS_FAV_ATTR k_fav_pair_lq16(const 
   else
     st = chk;
   if (tid == 0) status[g] = st;
+}
+
+// The wire-format call's H(m): column g of the workspace that k_fav_prep8 filled.
+struct fav_h_ws {
+  const uint32_t* ws;
+  uint64_t G;
+  __device__ __forceinline__ void load(g2a& hm, uint64_t g) const { soa_load<48>(&hm.x.c0.v[0], ws + 24 * G, G, g); }
+};
+
+__global__ void __launch_bounds__(kHexBlock) BLS_FAV_ATTR k_fav_pair_lq16(const uint32_t* __restrict__ pts,
+                                                             const int32_t* __restrict__ kcode, uint64_t nkeys,
+                                                             const uint64_t* __restrict__ goff,
+                                                             const uint32_t* __restrict__ ws, uint64_t G,
+                                                             int32_t* __restrict__ status) {
+  __shared__ uint32_t red[kHexBlock * 36];
+  __shared__ int sh_bad, sh_inf;
+  fav_pair_lq16_body(fav_wire_keys{pts, kcode, nkeys}, fav_h_ws{ws, G}, goff, ws, G, status, red, sh_bad, sh_inf);
+}
+
+// k_fav_pair_lq16 for the call with keys by table index (hipbls_verify_aggregate_batch_keys[_device]; hipbls.hip
+// launch_fav_keys): key k is table[key_idx[k]], no decode and no subgroup test; ws holds the signatures and their codes
+// only (verify_lat.hip k_verify_prep8_keys), and each group's H(m) is read where it lies (fav_keys.h fav_h_cols: a
+// column of the H(m) cache, or of the call's own table), so no gather runs in between.  A group that the host cut into
+// slices adds its slices' partial sums (kernels.h k_fav_sum_keys) instead of walking its keys.
+__global__ void __launch_bounds__(kHexBlock) BLS_FAV_ATTR k_fav_pair_lq16_keys(
+    const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+    const uint32_t* __restrict__ tab, const uint64_t* __restrict__ poff, const uint32_t* __restrict__ parts,
+    const int32_t* __restrict__ pflags, uint64_t n_slices, const uint64_t* __restrict__ goff,
+    const uint32_t* __restrict__ hcol, const uint32_t* __restrict__ Hcache, uint64_t cstride,
+    const uint32_t* __restrict__ Hc, uint64_t hstride, const uint32_t* __restrict__ ws, uint64_t G,
+    int32_t* __restrict__ status) {
+  __shared__ uint32_t red[kHexBlock * 36];
+  __shared__ int sh_bad, sh_inf;
+  fav_pair_lq16_body(fav_tab_keys{key_idx, T, tcode, tab, poff, parts, pflags, n_slices},
+                     fav_h_cols{hcol, Hcache, cstride, Hc, hstride}, goff, ws, G, status, red, sh_bad, sh_inf);
 }
 
 #endif

@@ -117,6 +117,8 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_pubshare_table_load": ([u8p, u64, i32p], ctypes.c_int),
         "hipbls_verify_aggregate_batch": ([u8p, u64p, u64, u8p, u8p, u64p, i32p], ctypes.c_int),
         "hipbls_verify_aggregate_batch_device": ([vp, u64, vp, u64, vp, vp, vp, vp, vp], ctypes.c_int),
+        "hipbls_verify_aggregate_batch_keys": ([u32p, u64p, u64, u8p, u8p, u64p, i32p], ctypes.c_int),
+        "hipbls_verify_aggregate_batch_keys_device": ([vp, u64, vp, u64, vp, vp, vp, vp, vp], ctypes.c_int),
         "hipbls_pubshare_table_size": ([u64p], ctypes.c_int),
         "hipbls_verify_batch_keys": ([u32p, u8p, u64p, u8p, u64, i32p], ctypes.c_int),
         "hipbls_batch_verify_rlc_keys": ([u32p, u8p, u32p, u64, u8p, u64p, u64, u8p, i32p], ctypes.c_int),
@@ -161,6 +163,7 @@ def exported_symbols() -> List[str]:
         "hipbls_queue_worker_stats", "hipbls_set_latency_replicas", "hipbls_build_id",
         "hipbls_threshold_aggregate_verify_batch_keys", "hipbls_threshold_aggregate_verify_batch_keys_device",
         "hipbls_keycache_config", "hipbls_keycache_stats", "hipbls_hcache_prefetch",
+        "hipbls_verify_aggregate_batch_keys", "hipbls_verify_aggregate_batch_keys_device",
     ]
 
 
@@ -585,6 +588,36 @@ class HipBLS:
         _check(self.lib.hipbls_verify_aggregate_batch(b"".join(keys), koffs, g, b"".join(bytes(s) for _, s, _ in groups),
                                                       blob, moffs, st), self.lib)
         return list(st)[:g]
+
+    def batch_verify_aggregate_keys_status(self, groups: Sequence[Tuple[Sequence[int], bytes, bytes]]) -> List[int]:
+        """batch_verify_aggregate_status with each group's keys named by their indices in the loaded table: a group
+        is (key_idx, signature, data).  No key is decoded; H(m) of each distinct message is read from the H(m) cache
+        on a hit and hashed into a table of the call's own on a miss (the call never inserts)."""
+        g = len(groups)
+        for _, sig, _ in groups:
+            _check_lengths("signature", [sig], 96)
+        koffs = (ctypes.c_uint64 * (g + 1))()
+        idx: List[int] = []
+        for j, (key_idx, _, _) in enumerate(groups):
+            koffs[j] = len(idx)
+            idx.extend(int(k) for k in key_idx)
+        koffs[g] = len(idx)
+        blob, moffs = _offsets([bytes(d) for _, _, d in groups])
+        st = _status_array(g)
+        arr = (ctypes.c_uint32 * max(len(idx), 1))(*idx)
+        _check(self.lib.hipbls_verify_aggregate_batch_keys(arr, koffs, g, b"".join(bytes(s) for _, s, _ in groups),
+                                                           blob, moffs, st), self.lib)
+        return list(st)[:g]
+
+    def verify_aggregate_keys(self, key_idx: Sequence[int], signature: bytes, data: bytes) -> None:
+        """verify_aggregate with the public keys named by their indices in the loaded table; raises as it does."""
+        st = self.batch_verify_aggregate_keys_status([(key_idx, signature, data)])[0]
+        if st == ERR_SIGNATURE:
+            raise TBLSError("cannot unmarshal signature into Herumi signature")
+        if st == ERR_PUBKEY:
+            raise TBLSError("cannot set compressed public key in Herumi format")
+        if st != OK:
+            raise TBLSError("signature verification failed")
 
     def aggregate(self, signs: Sequence[bytes]) -> bytes:
         """herumi.go:220-242: the G2 sum; the only error is a signature that does not deserialize.  An empty

@@ -34,6 +34,14 @@ its calls, so the row is an upper bound).  Back to back, the two threads take th
 turns, so the row's max_ms and pass_wall_ms show starvation rather than one collision; the _beside_paced_prefetch_<N>
 rows rest the other thread 5 ms between its calls, so that a clocked call waits for at most one prefetch.
 
+The fav_keys_* shapes are the lone FastAggregateVerify by key index (hipbls_verify_aggregate_batch_keys, DESIGN.md
+4.7.1) beside the wire-format fav_* rows over the same keys: 4, 12 and 512 keys, _warm on a prefetched root (the call
+only reads the cache, so it stays warm) and _nocache with the cache disabled (the call hashes the root itself).  The
+lock shape is cluster/lock.go:162-178 for 10,000 validators x 4 shares: one group of 40,000 keys (--lock-keys), wire
+format (fav_lock_<N>), keyed with the split key sum at its default threshold (fav_keys_lock_<N>) and keyed with the
+split off (fav_keys_lock_<N>_nosplit).  HIPBLS_FAV_SUM_SPLIT is read at init, so the last row comes from a child
+process of this tool run with HIPBLS_FAV_SUM_SPLIT=0 and the one shape.
+
 --shapes takes name prefixes (comma-separated) to run a subset.
 """
 import argparse
@@ -42,6 +50,7 @@ import json
 import os
 import random
 import statistics
+import subprocess
 import sys
 import threading
 import time
@@ -53,7 +62,8 @@ STAGES = ("verify_prep8", "verify_pair_lq16", "verify_pair_lq8", "fav_prep8", "f
           "tagg_sum8", "tv_phase_a", "tv_prep_pk", "tagg_scale", "tagg_sum", "tv_check_unscale", "tagg_unscale",
           "verify_pair_lq4", "verify_pair_lg2", "tv_prep8_keys", "tv_gather_keys", "tv_phase_a_keys",
           "verify_prep8_keys", "verify_gather_keys", "verify_keys", "rlc_hash", "rlc_items", "rlc_window",
-          "rlc_window_lg2", "hcache_fill8")
+          "rlc_window_lg2", "hcache_fill8", "fav_prep8_keys", "fav_lq16_keys", "fav_keys", "fav_sum_keys")
+FAV_SIZES = (4, 12, 512)
 SIZES = (8, 64, 512, 4096)
 PREFETCH_SIZES = (1, 64, 4097)
 BESIDE_SIZES = (1, 4096)
@@ -96,6 +106,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--timing-calls", type=int, default=20)
     ap.add_argument("--shapes", default="", help="comma-separated name prefixes; default: every shape")
+    ap.add_argument("--lock-keys", type=int, default=40000, help="keys of the lock-shape FastAggregateVerify group")
     a = ap.parse_args()
     if a.calls < 200:
         ap.error("--calls must be at least 200")
@@ -106,6 +117,18 @@ def main():
     (d46, d710, d710b), shares = [m[0] for m in made], [m[1] for m in made]
     share_secrets = made[0][2]  # duty 0's four share secrets, in the order of its sorted ids
     fav4, fav12 = _fav(impl, rng, 4), _fav(impl, rng, 12)
+    # the keyed FastAggregateVerify shapes; the large groups are only made when a shape that uses them is selected
+    prefixes = tuple(a.shapes.split(",")) if a.shapes else ("",)
+    lock_name = "lock_%d" % a.lock_keys
+
+    def selected(*names):
+        return any(n.startswith(prefixes) for n in names)
+
+    favs = {4: fav4, 12: fav12}
+    if selected("fav_1x512", "fav_keys_1x512"):
+        favs[512] = _fav(impl, rng, 512)
+    if selected("fav_" + lock_name, "fav_keys_" + lock_name):
+        favs[lock_name] = _fav(impl, random.Random(0x10C), a.lock_keys)
 
     def verify(d):  # a Verify of the duty's aggregate: the randao / block signature check
         assert impl.batch_verify_status([d[1]], [d[2]], [d[3]]) == [0]
@@ -134,7 +157,19 @@ def main():
         table.extend(sh[i] for i in sorted(sh))
         root_idx.append(len(table))
         table.append(d[1])
+    fav_idx = {}
+    for size, f in favs.items():
+        fav_idx[size] = list(range(len(table), len(table) + len(f[0])))
+        table.extend(f[0])
     assert set(impl.load_pubshares(table)) == {0}
+
+    def fav_keys(size):
+        f = favs[size]
+        assert impl.batch_verify_aggregate_keys_status([(fav_idx[size], f[1], f[2])]) == [0]
+
+    def fav_warm(size):  # the root hashed ahead of the call, which only reads the cache
+        cache(65536)
+        assert impl.hcache_prefetch([favs[size][2]]) == (1, 0)
 
     def warm(k):  # parsigex's keyed RLC BatchVerify over the duty's partials: caches H(root)
         d = duties[k]
@@ -233,6 +268,14 @@ def main():
               ("queued_verify_keyed_cold", lambda: verify_queued(1)),
               ("queued_verify_keyed_warm", lambda: verify_queued(1)),
               ("chain_verify_keys_sigagg_keys_x2", chain_keys_all)]
+    for size in favs:
+        tag = "1x%d" % size if isinstance(size, int) else size
+        if size not in (4, 12):
+            shapes.append(("fav_" + tag, lambda size=size: fav(favs[size])))
+        shapes.append(("fav_keys_%s_warm" % tag if isinstance(size, int) else "fav_keys_" + tag,
+                       lambda size=size: fav_keys(size)))
+        if isinstance(size, int):
+            shapes.append(("fav_keys_%s_nocache" % tag, lambda size=size: fav_keys(size)))
     for n in SIZES:
         shapes.append(("verify_keys_n%d" % n, lambda n=n: verify_keys_n(n)))
         shapes.append(("verify_keys_n%d_warm" % n, lambda n=n: verify_keys_n(n)))
@@ -251,6 +294,12 @@ def main():
              "sigagg_keys_7of10_nocache": lambda: cache(0), "chain_verify_sigagg_keys_x2": lambda: cache(65536, (1, 2)),
              "verify_keys_1_warm": lambda: cache(65536), "verify_keys_1_nocache": lambda: cache(0),
              "queued_verify_keyed_warm": lambda: cache(65536)}
+    for size in favs:
+        if isinstance(size, int):
+            setup["fav_keys_1x%d_warm" % size] = lambda size=size: fav_warm(size)
+            setup["fav_keys_1x%d_nocache" % size] = lambda: cache(0)
+        else:
+            setup["fav_keys_" + size] = lambda size=size: fav_warm(size)
     for n in SIZES:
         setup["verify_keys_n%d" % n] = lambda: cache(0)
         setup["verify_keys_n%d_warm" % n] = lambda: cache(65536)
@@ -316,6 +365,16 @@ def main():
     finally:
         impl.lib.hipbls_set_timing(0)
         impl.hcache_config(0)
+    # the lock shape with the split key sum off: HIPBLS_FAV_SUM_SPLIT is read at init, so another process
+    nosplit = "fav_keys_%s_nosplit" % lock_name
+    if lock_name in favs and selected(nosplit) and os.environ.get("HIPBLS_FAV_SUM_SPLIT") is None:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--calls", str(a.calls), "--warmup", str(a.warmup),
+                            "--timing-calls", str(a.timing_calls), "--lock-keys", str(a.lock_keys), "--shapes",
+                            "fav_keys_" + lock_name], env=dict(os.environ, HIPBLS_FAV_SUM_SPLIT="0"),
+                           capture_output=True, text=True, check=True)
+        child = json.loads(r.stdout.strip().splitlines()[-1])
+        out["shapes"][nosplit] = child["shapes"]["fav_keys_" + lock_name]
+        out["kernels_ms"][nosplit] = child["kernels_ms"]["fav_keys_" + lock_name]
     print(json.dumps(out, sort_keys=True))
 
 

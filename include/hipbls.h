@@ -200,6 +200,25 @@ int hipbls_verify_aggregate_batch(const uint8_t* pks, const uint64_t* key_offset
                                   const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
                                   int32_t* status);
 
+/* hipbls_verify_aggregate_batch with key k of the call = table[key_idx[k]] (hipbls_pubshare_table_load): group g checks
+ * sigs[96 g ..] over message g against the keys table[key_idx[k]], k in [key_offsets[g], key_offsets[g+1]).  status[g]
+ * is exactly what the wire-format call returns for the same key bytes, in every pair mode: the signature's encoding or
+ * G2-membership error first, then a table entry that failed to load (HIPBLS_ERR_PUBKEY), then HIPBLS_ERR_VERIFY (also
+ * for an empty group, the identity key, a key sum at infinity).  No key is decompressed or subgroup-tested: the table
+ * load did that once.  The groups' messages are folded to the distinct ones, and each of those is looked up in the
+ * context's H(m) cache (hipbls_hcache_config; counted per distinct message in hipbls_hcache_stats): a hit is read from
+ * its column, a miss is hashed once into a table of the call's own, also with the cache disabled or smaller than the
+ * call's distinct messages.  The call only reads the cache (FastAggregateVerify is the last consumer of a root): it
+ * never inserts or evicts.  HIPBLS_ERR_ARG for the whole call, before anything is launched, when a key index is outside
+ * the table.  Routes as the wire-format call's: at most 16 groups in AUTO pair mode are timed as "fav_prep8_keys" +
+ * "fav_lq16_keys", anything else as "rlc_hash" (the missing hashes) + "fav_keys".  A group of more than 2,048 keys
+ * (the cluster lock's aggregate over every pubshare) is cut into slices of that many keys, each summed by a workgroup
+ * of its own ("fav_sum_keys") before the check adds the partial sums; the environment variable HIPBLS_FAV_SUM_SPLIT,
+ * read at init, overrides the threshold, 0 turns the split off.  Statuses do not depend on it. */
+int hipbls_verify_aggregate_batch_keys(const uint32_t* key_idx, const uint64_t* key_offsets, uint64_t n_groups,
+                                       const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                       int32_t* status);
+
 /* herumi's Deserialize of n points, one status each: kind 1 = 48-byte public keys (OK | ERR_PUBKEY), kind 2 = 96-byte
  * signatures (OK | ERR_SIGNATURE); flags, x < p, on the curve, in the subgroup (the point at infinity deserializes).
  * The Go binding uses it to name the failing item in Aggregate / ThresholdAggregate errors, the
@@ -379,6 +398,13 @@ int hipbls_verify_aggregate_batch_device(const uint8_t* d_pks, uint64_t nkeys, c
                                          uint64_t n_groups, const uint8_t* d_sigs, const uint8_t* d_msgs,
                                          const uint64_t* d_msg_offsets, int32_t* d_status, void* stream);
 
+/* Device variant of hipbls_verify_aggregate_batch_keys (nkeys = key_offsets[n_groups], passed explicitly).  The host
+ * never sees the messages, so each group's message is hashed and the H(m) cache is untouched.  A key index outside the
+ * table yields status[g] = HIPBLS_ERR_ARG for that group only. */
+int hipbls_verify_aggregate_batch_keys_device(const uint32_t* d_key_idx, uint64_t nkeys, const uint64_t* d_key_offsets,
+                                              uint64_t n_groups, const uint8_t* d_sigs, const uint8_t* d_msgs,
+                                              const uint64_t* d_msg_offsets, int32_t* d_status, void* stream);
+
 /* Device variants of the *_keys calls: an out-of-range key or message index yields
  * status[i] = HIPBLS_ERR_ARG. */
 int hipbls_verify_batch_keys_device(const uint32_t* d_key_idx, const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
@@ -393,7 +419,9 @@ int hipbls_batch_verify_rlc_keys_device(const uint32_t* d_key_idx, const uint8_t
  * "rlc_hash", "rlc_window" / "rlc_window_lg2", "rlc_fallback" / "rlc_fallback_lg2", "tagg_scale", "tagg_sum",
  * "fav"; sigagg in one call: "tv_phase_a", "tv_check_unscale", "tv_prep8", "tv_lq16", and with keys by index
  * "tv_phase_a_keys", "tv_prep8_keys", "tv_gather_keys"; the keyed Verify latency route: "verify_prep8_keys",
- * "verify_gather_keys" (then "verify_pair_lq16" / "verify_pair_lq8" as the wire-format call). */
+ * "verify_gather_keys" (then "verify_pair_lq16" / "verify_pair_lq8" as the wire-format call); FastAggregateVerify
+ * on the lone route: "fav_prep8", "fav_lq16", and with keys by index "fav_prep8_keys", "fav_lq16_keys", "fav_keys",
+ * "fav_sum_keys". */
 int hipbls_kernel_timing(const char* name, double* avg_ms, uint64_t* launches);
 int hipbls_kernel_timing_reset(void);
 

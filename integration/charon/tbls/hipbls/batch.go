@@ -163,19 +163,31 @@ func (h HipBLS) BatchVerifyAggregate(keys [][]tbls.PublicKey, sigs []tbls.Signat
 		return nil, errors.New("mismatching lengths")
 	}
 	var flatKeys []byte
+	var allKeys []tbls.PublicKey
 	koffs := make([]uint64, g+1)
 	for i, ks := range keys {
 		for _, k := range ks {
 			flatKeys = append(flatKeys, k[:]...)
 		}
+		allKeys = append(allKeys, ks...)
 		koffs[i+1] = uint64(len(flatKeys) / 48)
 	}
 	flat, moffs := flatten(msgs)
 	status := make([]int32, g)
-	rc := C.hipbls_verify_aggregate_batch(u8(flatKeys), u64(koffs), C.uint64_t(g),
-		(*C.uint8_t)(unsafe.Pointer(&sigs[0][0])), u8(flat), u64(moffs), i32(status))
+	var rc C.int
+	path := "batch_verify_aggregate"
+	kidx, keyed, release := lockTable(allKeys) // held across the call, as in BatchVerify
+	if keyed && len(allKeys) > 0 { // every key of every group by resident table index: no decode, H(m) from the cache
+		path = "batch_verify_aggregate_keys"
+		rc = C.hipbls_verify_aggregate_batch_keys((*C.uint32_t)(unsafe.Pointer(&kidx[0])), u64(koffs), C.uint64_t(g),
+			(*C.uint8_t)(unsafe.Pointer(&sigs[0][0])), u8(flat), u64(moffs), i32(status))
+	} else {
+		rc = C.hipbls_verify_aggregate_batch(u8(flatKeys), u64(koffs), C.uint64_t(g),
+			(*C.uint8_t)(unsafe.Pointer(&sigs[0][0])), u8(flat), u64(moffs), i32(status))
+	}
+	release()
 	if rc != C.HIPBLS_OK {
-		return nil, observeFailure("batch_verify_aggregate", g, devErr(rc))
+		return nil, observeFailure(path, g, devErr(rc))
 	}
 	errs := make([]error, g)
 	for i, s := range status {
@@ -189,7 +201,7 @@ func (h HipBLS) BatchVerifyAggregate(keys [][]tbls.PublicKey, sigs []tbls.Signat
 			errs[i] = errors.New("signature verification failed")
 		}
 	}
-	observe("batch_verify_aggregate", errs)
+	observe(path, errs)
 
 	return errs, nil
 }

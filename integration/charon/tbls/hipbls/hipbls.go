@@ -468,17 +468,34 @@ func (h HipBLS) ThresholdAggregate(parts map[int]tbls.Signature) (tbls.Signature
 
 // VerifyAggregate: FastAggregateVerify (tbls/herumi.go:315-339); an empty key list is "signature verification
 // failed".
+//
+// When every share is in the resident pubshare table (the cluster lock's aggregate over all pubshares, cluster/lock.go:
+// 162-178; the sync committee's fixed keys) the call names them by table index: no key is decoded or subgroup-tested
+// again, and H(m) is read from the H(m) cache when an earlier call or a prefetch left it there.  Same statuses.
 func (HipBLS) VerifyAggregate(shares []tbls.PublicKey, sig tbls.Signature, data []byte) error {
 	keys := make([]byte, 0, 48*len(shares))
 	for _, s := range shares {
 		keys = append(keys, s[:]...)
 	}
 	status := make([]int32, 1)
-	if rc := C.hipbls_verify_aggregate(u8(keys), C.uint64_t(len(shares)), u8(sig[:]), u8(data), C.uint64_t(len(data)),
-		i32(status)); rc != C.HIPBLS_OK {
-		return observeFailure("verify_aggregate", 1, devErr(rc))
+	var rc C.int
+	path := "verify_aggregate"
+	kidx, keyed, release := lockTable(shares) // held across the call, as in BatchVerify
+	if keyed && len(shares) > 0 {
+		path = "verify_aggregate_keys"
+		koffs := []uint64{0, uint64(len(shares))}
+		moffs := []uint64{0, uint64(len(data))}
+		rc = C.hipbls_verify_aggregate_batch_keys((*C.uint32_t)(unsafe.Pointer(&kidx[0])), u64(koffs), 1, u8(sig[:]),
+			u8(data), u64(moffs), i32(status))
+	} else {
+		rc = C.hipbls_verify_aggregate(u8(keys), C.uint64_t(len(shares)), u8(sig[:]), u8(data), C.uint64_t(len(data)),
+			i32(status))
 	}
-	observeStatus("verify_aggregate", 1, status[0] != C.HIPBLS_OK)
+	release()
+	if rc != C.HIPBLS_OK {
+		return observeFailure(path, 1, devErr(rc))
+	}
+	observeStatus(path, 1, status[0] != C.HIPBLS_OK)
 	switch C.int32_t(status[0]) {
 	case C.HIPBLS_OK:
 		return nil

@@ -87,6 +87,15 @@ func TestMetricsCountEveryEntryPoint(t *testing.T) {
 	_, err = h.BatchVerify(pks, msgs, sigs)
 	require.NoError(t, err)
 	require.InDelta(t, n, items("batch_verify_keys")-i0, 0)
+	// every key of every group in the table: FastAggregateVerify by table index
+	i0 = items("batch_verify_aggregate_keys")
+	_, err = h.BatchVerifyAggregate([][]tbls.PublicKey{pks[:1], pks[3:5]}, []tbls.Signature{sigs[0], sigs[3]},
+		[][]byte{root, root})
+	require.NoError(t, err)
+	require.InDelta(t, 2, items("batch_verify_aggregate_keys")-i0, 0)
+	i0 = items("verify_aggregate_keys")
+	require.NoError(t, h.VerifyAggregate(pks[:1], sigs[0], root))
+	require.InDelta(t, 1, items("verify_aggregate_keys")-i0, 0)
 	require.NoError(t, h.LoadPubShares(nil))
 }
 

@@ -18,7 +18,9 @@ import (
 // path label tells which GPU route charon's callers reach: "verify" (the submission queue behind tbls.Verify),
 // "batch_verify" / "batch_verify_keys" (wire-format keys or the resident pubshare table), "batch_verify_rlc" /
 // "batch_verify_rlc_keys" (random-linear-combination checks over shared roots), "threshold_aggregate",
-// "fused_sigagg" (BatchThresholdAggregateVerify), "verify_aggregate", "batch_verify_aggregate" and "aggregate".
+// "fused_sigagg" (BatchThresholdAggregateVerify), "verify_aggregate" / "verify_aggregate_keys" and
+// "batch_verify_aggregate" / "batch_verify_aggregate_keys" (FastAggregateVerify over wire-format keys or table
+// indices) and "aggregate".
 var (
 	itemsCounter = promauto.NewCounterVec(prometheus.CounterOpts{
 		Namespace: "tbls",
