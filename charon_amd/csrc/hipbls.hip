@@ -187,6 +187,36 @@ struct KeyCache {
 constexpr uint64_t kKeyCacheDefaultSlots = 65536;  // x 256 B = 16 MiB per context; a cluster's 4,096 pubshares load it to 6 %
 constexpr uint64_t kKeyCacheMaxSlots = 1ull << 24;
 
+// Resident root cache (rootcache.h): a 32-byte signing root -> H(m), looked up by k_root_lookup and
+// read and filled by k_verify_fused.  The host owns the buffers and the generations: `mu` is held across "copy the
+// struct, enqueue the lookup and the fused kernel" (launch_verify_fused) and by config and the rollover from before
+// they wait for the device until the buffers are zeroed -- KeyCache::mu's pattern.  Lock order: the context's mu
+// (where held), this one, then KeyCache::mu.
+struct RootCache {
+  std::mutex mu;
+  uint64_t slots = 0;  // power of two; 0 = off
+  uint32_t* entries = nullptr;
+  uint32_t* claim = nullptr;
+  unsigned long long* ctr = nullptr;  // hits, misses, inserts (all since the last config)
+  // pinned: the device's insert counter as of the last fused kernel whose stream has reached the copy behind it
+  unsigned long long* h_ins = nullptr;
+  uint64_t gen_base = 0;   // the insert counter when this generation began
+  uint64_t rollovers = 0;  // generations ended since the last config
+  bool partition = true;   // hits to the front (HIPBLS_ROOTCACHE_PARTITION=0: identity order)
+  bls::rootcache dev() const {
+    bls::rootcache r{};
+    if (slots) {
+      r.entries = entries;
+      r.claim = claim;
+      r.ctr = ctr;
+      r.mask = (uint32_t)(slots - 1);
+    }
+    return r;
+  }
+};
+constexpr uint64_t kRootCacheDefaultSlots = 262144;  // x 256 B = 64 MiB (+ 1 MiB of claims) per context
+constexpr uint64_t kRootCacheMaxSlots = 1ull << 22;
+
 // One open or running batch of the submission queue.
 struct VBatch {
   std::vector<uint8_t> pk, sig, msg;
@@ -329,6 +359,7 @@ struct Context {
   uint64_t rlcb_attempted = 0, rlcb_passed = 0;
   HCache hcache;
   KeyCache kcache;
+  RootCache rcache;
   std::mutex tmu;                            // timing table (also used by the queue worker)
   std::map<std::string, TimingSlot> timing;  // per kernel name: HIP events on the launch stream
   VerifyQueue q;
@@ -400,6 +431,53 @@ uint64_t keycache_default_slots() {
   if (end == e || *end || v > kKeyCacheMaxSlots) {
     fprintf(stderr, "hipbls: HIPBLS_KEYCACHE_SLOTS=%s ignored (expected 0 .. 2^24)\n", e);
     return kKeyCacheDefaultSlots;
+  }
+  return (uint64_t)v;
+}
+
+// The root cache's counterpart of keycache_setup: `slots` slots (0: off; rounded up to a power of two, at least a
+// probe window), all empty, counters and generation state zero.  RootCache::mu is held, the context's device is
+// current and no kernel that takes the cache runs or can be enqueued.
+int rootcache_setup(RootCache& rc, uint64_t slots, hipStream_t s) {
+  if (slots > kRootCacheMaxSlots) return arg_err("root cache above 2^22 slots");
+  uint64_t want = 0;
+  if (slots) {
+    want = bls::KC_MIN_SLOTS;
+    while (want < slots) want <<= 1;
+  }
+  if (want != rc.slots) {
+    if (rc.entries) (void)hipFree(rc.entries);
+    if (rc.claim) (void)hipFree(rc.claim);
+    rc.entries = rc.claim = nullptr;
+    rc.slots = 0;
+    if (want) {
+      HIP_TRY(hipMalloc((void**)&rc.entries, want * bls::RC_WORDS * 4));
+      HIP_TRY(hipMalloc((void**)&rc.claim, want * 4));
+      rc.slots = want;
+    }
+  }
+  if (!rc.ctr) HIP_TRY(hipMalloc((void**)&rc.ctr, 3 * sizeof(unsigned long long)));
+  if (!rc.h_ins) HIP_TRY(hipHostMalloc((void**)&rc.h_ins, sizeof(unsigned long long), hipHostMallocDefault));
+  HIP_TRY(hipMemsetAsync(rc.ctr, 0, 3 * sizeof(unsigned long long), s));
+  if (rc.slots) {
+    HIP_TRY(hipMemsetAsync(rc.claim, 0, rc.slots * 4, s));
+    HIP_TRY(hipMemsetAsync(rc.entries, 0, rc.slots * bls::RC_WORDS * 4, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  *rc.h_ins = 0;
+  rc.gen_base = 0;
+  rc.rollovers = 0;
+  return HIPBLS_OK;
+}
+// HIPBLS_ROOTCACHE_SLOTS overrides the default size; 0 turns the cache off.
+uint64_t rootcache_default_slots() {
+  const char* e = getenv("HIPBLS_ROOTCACHE_SLOTS");
+  if (!e || !e[0]) return kRootCacheDefaultSlots;
+  char* end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  if (end == e || *end || v > kRootCacheMaxSlots) {
+    fprintf(stderr, "hipbls: HIPBLS_ROOTCACHE_SLOTS=%s ignored (expected 0 .. 2^22)\n", e);
+    return kRootCacheDefaultSlots;
   }
   return (uint64_t)v;
 }
@@ -477,6 +555,7 @@ const KernelRef kKernels[] = {
     KREF(k_tv_phase_a_keys), KREF(k_tv_join_keys), KREF(k_tv_gather_keys), KREF8(k_tv_prep8_keys),
     KREF(k_verify_gather_keys), KREF8(k_verify_prep8_keys), KREF8(k_hcache_fill8),
     KREF(k_fav_batch_keys), KREF16W(k_fav_pair_lq16_keys), KREF(k_fav_sum_keys),
+    KREF(k_root_lookup),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -636,6 +715,10 @@ int init_locked(const std::vector<int>& ids) {
     {
       const int krc = keycache_setup(c->kcache, keycache_default_slots(), c->stream);
       if (krc) return krc;
+      const char* part = getenv("HIPBLS_ROOTCACHE_PARTITION");
+      c->rcache.partition = !(part && part[0] == '0');
+      const int rrc = rootcache_setup(c->rcache, rootcache_default_slots(), c->stream);
+      if (rrc) return rrc;
     }
     made.push_back(c);
   }
@@ -1039,12 +1122,13 @@ bool use_octets(uint64_t n) {
 // fixed place per allocation, 64-byte aligned since the capacity is a multiple of 256, beyond every batch's data;
 // zeroed when the buffer is allocated, then only ever written with a launch's epoch, so a stale word never equals a
 // new epoch)
-int verify_ws_ensure(DevBuf& ws, uint64_t n, hipStream_t s) {
+int verify_ws_ensure_bytes(DevBuf& ws, uint64_t bytes, hipStream_t s) {
   void* const before = ws.p;
-  HIP_TRY(ws.ensure(n * 122 * 4 + 128));
+  HIP_TRY(ws.ensure(bytes + 128));
   if (ws.p != before) HIP_TRY(hipMemsetAsync((uint8_t*)ws.p + ws.cap - 64, 0, 64, s));
   return HIPBLS_OK;
 }
+int verify_ws_ensure(DevBuf& ws, uint64_t n, hipStream_t s) { return verify_ws_ensure_bytes(ws, n * 122 * 4, s); }
 
 // A batch of one workgroup (<= 8 items: the drop-in n = 1 calls) races `lat_replicas` copies of it, one per XCD
 // (verify_lat.hip bls_race): the first copy to finish each stage wins.  Race words after the workspace.
@@ -1083,17 +1167,82 @@ int launch_oct_check(Context& c, const DevBuf& ws, uint64_t n, int32_t* d_status
   });
 }
 
-// Verify: fused (one lane per item) or prep + lane-pair check; `ws` is the caller's SoA workspace for the latter
-// (120 words per item), so the library stream and the queue worker never share one.
+// Whether the root cache's generation is due to end: the last insert count a finished call reported has reached half
+// the slots.  RootCache::mu held.
+bool rootcache_due(const RootCache& R) {
+  return R.slots && *(volatile unsigned long long*)R.h_ins - R.gen_base >= R.slots / 2;
+}
+
+// Roots age, so a half-full root cache is emptied before the next call that would use it: both
+// locks, a wait for the device (every kernel that took the cache was enqueued under its lock, so none runs afterwards
+// and none can be enqueued until the lock is released), then the claims and the entries are zeroed on the library
+// stream.  ctx_locked: the caller holds the context's lock (every caller but the submission queue's worker).
+int rootcache_roll_if_due(Context& c, bool ctx_locked) {
+  RootCache& R = c.rcache;
+  {
+    std::lock_guard<std::mutex> g(R.mu);
+    if (!rootcache_due(R)) return HIPBLS_OK;
+  }
+  std::unique_lock<std::mutex> cl(c.mu, std::defer_lock);
+  if (!ctx_locked) cl.lock();
+  std::lock_guard<std::mutex> g(R.mu);
+  if (!rootcache_due(R)) return HIPBLS_OK;  // another caller ended the generation, or config replaced the table
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long ins = 0;
+  HIP_TRY(hipMemcpyAsync(&ins, R.ctr + 2, sizeof(ins), hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipMemsetAsync(R.claim, 0, R.slots * 4, c.stream));
+  HIP_TRY(hipMemsetAsync(R.entries, 0, R.slots * bls::RC_WORDS * 4, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  *R.h_ins = ins;
+  R.gen_base = ins;
+  R.rollovers += 1;
+  return HIPBLS_OK;
+}
+
+// The fused route: one lane per item (k_verify_fused), behind the root cache's lookup stage when the cache is on.
+// perm, pslot and the lookup's two counters live in `ws` (the caller's, so no two streams share them).
+int launch_verify_fused(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_offs,
+                        const uint8_t* d_sigs, uint64_t n, int32_t* d_status, hipStream_t s, DevBuf& ws,
+                        bool ctx_locked) {
+  RootCache& R = c.rcache;
+  int rc = rootcache_roll_if_due(c, ctx_locked);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> rg(R.mu);
+  const bls::rootcache rcd = n <= 0xffffffffull ? R.dev() : bls::rootcache{};  // perm holds 32-bit indices
+  uint32_t *perm = nullptr, *pslot = nullptr;
+  if (rcd.entries) {
+    rc = verify_ws_ensure_bytes(ws, (2 * n + 2) * 4, s);  // perm[n], pslot[n], the two counters
+    if (rc) return rc;
+    perm = (uint32_t*)ws.p;
+    pslot = perm + n;
+    uint32_t* const cnt = pslot + n;
+    HIP_TRY(hipMemsetAsync(cnt, 0, 2 * sizeof(uint32_t), s));
+    rc = timed(c, "root_lookup", s, [&] {
+      hipLaunchKernelGGL(k_root_lookup, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_msgs, d_offs, n, rcd, perm,
+                         pslot, cnt, R.partition ? 1 : 0);
+    });
+    if (rc) return rc;
+  }
+  rc = timed(c, "verify", s, [&] {
+    KC_LAUNCH_GUARD(c);
+    hipLaunchKernelGGL(k_verify_fused, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs, d_sigs,
+                       n, d_status, c.kcache.dev(), rcd, (const uint32_t*)perm, (const uint32_t*)pslot);
+  });
+  if (rc) return rc;
+  // the insert counter, for the next call's generation check: a copy behind the kernel, never waited for
+  if (rcd.entries) HIP_TRY(hipMemcpyAsync(R.h_ins, rcd.ctr + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  return HIPBLS_OK;
+}
+
+// Verify: fused (one lane per item) or prep + lane-pair check; `ws` is the caller's workspace (the fused route's
+// order and slots; 120 words per item of SoA points for the latter), so the library stream and the queue worker never
+// share one.  ctx_locked: whether the caller holds the context's lock (rootcache_roll_if_due).
 int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_offs,
-                  const uint8_t* d_sigs, uint64_t n, int32_t* d_status, hipStream_t s, DevBuf& ws) {
+                  const uint8_t* d_sigs, uint64_t n, int32_t* d_status, hipStream_t s, DevBuf& ws,
+                  bool ctx_locked = true) {
   if (n == 0) return HIPBLS_OK;
   if (!use_pairs(n, kLg2MaxVerify))
-    return timed(c, "verify", s, [&] {
-      KC_LAUNCH_GUARD(c);
-      hipLaunchKernelGGL(k_verify_fused, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs,
-                         d_sigs, n, d_status, c.kcache.dev());
-    });
+    return launch_verify_fused(c, d_pks, d_msgs, d_offs, d_sigs, n, d_status, s, ws, ctx_locked);
   int rc = verify_ws_ensure(ws, n, s);
   if (rc) return rc;
   if (use_octets(n)) {
@@ -2363,7 +2512,8 @@ int wire_launch(Context& c, QSlot& k, VBatch& b) {
   if (b.msg.size()) HIP_TRY(hipMemcpyAsync(k.d_msg.p, b.msg.data(), b.msg.size(), hipMemcpyHostToDevice, k.stream));
   HIP_TRY(hipMemcpyAsync(k.d_off.p, b.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, k.stream));
   int rc = launch_verify(c, (const uint8_t*)k.d_pk.p, (const uint8_t*)k.d_msg.p, (const uint64_t*)k.d_off.p,
-                         (const uint8_t*)k.d_sig.p, n, (int32_t*)k.d_st.p, k.stream, k.d_ws);
+                         (const uint8_t*)k.d_sig.p, n, (int32_t*)k.d_st.p, k.stream, k.d_ws,
+                         /*ctx_locked=*/false);  // the worker launches wire batches without the context lock
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(k.h_st, k.d_st.p, n * 4, hipMemcpyDeviceToHost, k.stream));
   HIP_TRY(hipEventRecord(k.done_ev, k.stream));
@@ -3812,6 +3962,40 @@ int hipbls_keycache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts) {
     *hits += v[0];
     *misses += v[1];
     *inserts += v[2];
+  }
+  return HIPBLS_OK;
+}
+
+int hipbls_rootcache_config(uint64_t slots) {
+  if (slots > kRootCacheMaxSlots) return arg_err("root cache above 2^22 slots");
+  ENSURE_INIT();
+  return run_all([&](Context& c) -> int {
+    // as hipbls_keycache_config: the context lock (run_all), then the cache's own, held from before the device wait
+    // until the new buffers stand
+    std::lock_guard<std::mutex> g(c.rcache.mu);
+    HIP_TRY(hipDeviceSynchronize());
+    return rootcache_setup(c.rcache, slots, c.stream);
+  });
+}
+
+int hipbls_rootcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, uint64_t* rollovers) {
+  if (!hits || !misses || !inserts || !rollovers) return arg_err("null output");
+  *hits = *misses = *inserts = *rollovers = 0;
+  ENSURE_INIT();
+  const int n = nctx();
+  for (int k = 0; k < n; ++k) {
+    Context& c = ctx(k);
+    ENTER_CTX(c);
+    std::lock_guard<std::mutex> g(c.rcache.mu);
+    if (!c.rcache.ctr) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    HIP_TRY(hipDeviceSynchronize());  // the counters of every call that has been enqueued
+    HIP_TRY(hipMemcpyAsync(v, c.rcache.ctr, sizeof(v), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    *hits += v[0];
+    *misses += v[1];
+    *inserts += v[2];
+    *rollovers += c.rcache.rollovers;
   }
   return HIPBLS_OK;
 }

@@ -28,17 +28,66 @@ __global__ void __launch_bounds__(kBlock) k_verify_fused(const uint8_t* __restri
                                                          const uint8_t* __restrict__ msgs,
                                                          const uint64_t* __restrict__ offs,
                                                          const uint8_t* __restrict__ sigs, uint64_t n,
-                                                         int32_t* __restrict__ status, keycache kc) {
-  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
+                                                         int32_t* __restrict__ status, keycache kc, rootcache rc,
+                                                         const uint32_t* __restrict__ perm,
+                                                         const uint32_t* __restrict__ pslot) {
+  const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  // k_root_lookup's order and slots (rootcache.h): lane j takes item perm[j].  perm == nullptr: identity, no root cache.
+  const uint64_t i = perm ? perm[j] : j;
+  if (i >= n) return;  // perm is a permutation of [0, n); nothing outside it is ever read or written
   const uint64_t o0 = offs[i], o1 = offs[i + 1];
 #if BLS_VERIFY_LDS
   BLS_LANE_F12(F);
-  // the key's decode goes through the key cache (keycache.h; kc.entries == nullptr: off)
-  status[i] = op_verify_l_kernel_kc(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i, F, kc);
+  // the key's decode goes through the key cache (keycache.h; kc.entries == nullptr: off), H(m) through the root cache
+  if (!perm) rc.entries = nullptr;
+  status[i] = op_verify_l_kernel_rc(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i, F, kc, rc,
+                                    perm ? pslot[j] : RC_NONE);
 #else
   status[i] = op_verify(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i);
 #endif
+}
+
+// The root cache's lookup stage (rootcache.h), one lane per item, before k_verify_fused: probe the
+// table for the item's root and record its slot (RC_NONE: not cached, or not eligible), and deal the items into an
+// order with the hits at the front and everything else at the back -- one ballot and one atomic per wave on each of
+// two counters, hits counting up from 0, the rest down from n - 1 -- so that at most one wave of the fused kernel
+// mixes hits and misses.  cnt[0], cnt[1]: zeroed before the launch.  partition == 0: identity order.  n < 2^32.
+// It ends before the fused kernel of its call starts, so a call never hits on its own inserts.
+__global__ void __launch_bounds__(kBlock) k_root_lookup(const uint8_t* __restrict__ msgs,
+                                                        const uint64_t* __restrict__ offs, uint64_t n, rootcache rc,
+                                                        uint32_t* __restrict__ perm, uint32_t* __restrict__ pslot,
+                                                        uint32_t* __restrict__ cnt, int partition) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t o0 = offs[i], o1 = offs[i + 1];
+  const bool eligible = o1 - o0 == RC_MSG_BYTES;
+  uint32_t slot = RC_NONE;
+  if (eligible) {
+    uint32_t tag[8];
+    rc_tag_from_msg(tag, msgs + o0);
+    slot = rc_find(rc, tag);
+  }
+  const bool hit = slot != RC_NONE;
+  rc_count(rc, 0, hit);
+  rc_count(rc, 1, eligible && !hit);
+  uint64_t pos = i;
+  if (partition) {
+    const uint64_t act = __ballot(1), mh = __ballot(hit), mr = act & ~mh;
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    uint32_t bh = 0, br = 0;
+    if (lane == (uint32_t)(__ffsll((unsigned long long)act) - 1)) {
+      if (mh) bh = atomicAdd(cnt + 0, (uint32_t)__popcll(mh));
+      if (mr) br = atomicAdd(cnt + 1, (uint32_t)__popcll(mr));
+    }
+    bh = __builtin_amdgcn_readfirstlane(bh);  // the first active lane's: the one that took the ranges
+    br = __builtin_amdgcn_readfirstlane(br);
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+    pos = hit ? (uint64_t)bh + __popcll(mh & below) : n - 1 - ((uint64_t)br + __popcll(mr & below));
+  }
+  if (pos >= n) return;  // cannot happen with zeroed counters; never write outside perm
+  perm[pos] = (uint32_t)i;
+  pslot[pos] = slot;
 }
 
 // ---------------------------------------------------------------- lane-pair Verify (lg2.h)

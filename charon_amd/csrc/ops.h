@@ -298,7 +298,7 @@ BLS_HD BLS_CALL int op_verify(const uint8_t* pk48, const uint8_t* msg, uint32_t 
 
 // op_verify with the Miller loop's f in LDS (F: this lane's slot; pairing_lds.h), in two parts: the key's decode
 // (dp: its DEC_* code with the subgroup test included) and the rest, so that a key served by the key cache (rlc.h
-// op_verify_l_kernel_kc) joins the same chain as one decoded here.
+// op_verify_l_kernel_rc) follows the same chain as one decoded here.
 template <int S, bool INL>
 BLS_HD BLS_INLINE int op_verify_l_rest(int dp, const g1a& pk, const uint8_t* msg, uint32_t msg_len,
                                        const uint8_t* sig96, const f12l<S> F) {

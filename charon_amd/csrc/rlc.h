@@ -17,6 +17,7 @@
 //   G1: [r] pk  = [a] pk  + [b] ([x] pk)       ([x] pk is the first half of the G1 subgroup test)
 #pragma once
 #include "keycache.h"
+#include "rootcache.h"
 #include "ops.h"
 
 namespace bls {
@@ -287,14 +288,42 @@ BLS_HD BLS_INLINE int tv_key_lane(g1a& lpk, uint64_t k, uint64_t T, const int32_
   return RLC_PENDING;
 }
 
-// k_verify_fused's form (ops.h op_verify_l_kernel) with the key decode behind the key cache: a hit and a miss join
-// the same kernel-inlined chain.
+// H(m) for Verify behind the root cache (rootcache.h): `slot` is what k_root_lookup recorded for this item (RC_NONE:
+// nothing).  A recorded slot's entry is loaded and verified against the message's own bytes; it then stands for
+// hash_to_g2 + jac_to_aff.  Otherwise the message is hashed as ever, and an eligible one (32 bytes) is published.
+// rc.entries == nullptr: the cache is off.
+BLS_HD BLS_CALL void verify_hm_rc(g2a& hm, const uint8_t* msg, uint32_t msg_len, const rootcache& rc, uint32_t slot) {
+  const bool eligible = rc.entries && msg_len == RC_MSG_BYTES;
+  uint32_t tag[8];
+  if (eligible) rc_tag_from_msg(tag, msg);
+  bool ins = false;
+  if (!(eligible && slot != RC_NONE && rc_get_slot(rc, slot, tag, &hm.x.c0.v[0]))) {
+    g2j hj;
+    hash_to_g2(hj, msg, msg_len, DST_POP, 43);
+    const bool inf = jac_is_inf(hj);
+    jac_to_aff(hm, hj);
+    if (eligible && !inf) ins = rc_insert(rc, tag, &hm.x.c0.v[0]);
+  }
+  if (rc.entries) rc_count(rc, 2, ins);
+}
+
+// k_verify_fused's form (ops.h op_verify_l_kernel: the same statuses in the same order as op_verify_l_rest, the whole
+// chain down to the Miller loop inlined into the kernel) with the key's decode behind the key cache and H(m) behind
+// the root cache: hits and misses of either join the same chain.
 template <int S>
-BLS_HD BLS_INLINE int op_verify_l_kernel_kc(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len,
-                                            const uint8_t* sig96, const f12l<S> F, const keycache& kc) {
+BLS_HD BLS_INLINE int op_verify_l_kernel_rc(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len,
+                                            const uint8_t* sig96, const f12l<S> F, const keycache& kc,
+                                            const rootcache& rc, uint32_t slot) {
   g1a pk;
   const int dp = g1_decode_kc_pk(pk, pk48, kc);
-  return op_verify_l_rest<S, true>(dp, pk, msg, msg_len, sig96, F);
+  if (dp == DEC_BAD) return HIPBLS_ERR_PUBKEY;
+  g2a sig;
+  const int ds = g2_decompress(sig, sig96, false);
+  if (ds == DEC_BAD) return HIPBLS_ERR_SIGNATURE;
+  if (dp == DEC_INF || ds == DEC_INF) return verify_inf_status(ds, sig);
+  g2a hm;
+  verify_hm_rc(hm, msg, msg_len, rc, slot);
+  return pairing_check_verify_sig_l_body<S, true>(pk, hm, sig, F);
 }
 
 // tbls.Verify with the public key taken from the table (same statuses as op_verify); the Miller loop's f in LDS.

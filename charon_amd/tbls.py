@@ -94,6 +94,8 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_hcache_prefetch": ([u8p, u64p, u64, u64p, u64p], ctypes.c_int),
         "hipbls_keycache_config": ([u64], ctypes.c_int),
         "hipbls_keycache_stats": ([u64p, u64p, u64p], ctypes.c_int),
+        "hipbls_rootcache_config": ([u64], ctypes.c_int),
+        "hipbls_rootcache_stats": ([u64p, u64p, u64p, u64p], ctypes.c_int),
         "hipbls_abi_version": ([], ctypes.c_int),
         "hipbls_init": ([ctypes.c_int], ctypes.c_int),
         "hipbls_device_count": ([], ctypes.c_int),
@@ -164,6 +166,7 @@ def exported_symbols() -> List[str]:
         "hipbls_threshold_aggregate_verify_batch_keys", "hipbls_threshold_aggregate_verify_batch_keys_device",
         "hipbls_keycache_config", "hipbls_keycache_stats", "hipbls_hcache_prefetch",
         "hipbls_verify_aggregate_batch_keys", "hipbls_verify_aggregate_batch_keys_device",
+        "hipbls_rootcache_config", "hipbls_rootcache_stats",
     ]
 
 
@@ -722,6 +725,18 @@ class HipBLS:
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self.lib.hipbls_keycache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), self.lib)
         return a.value, b.value, c.value
+
+    # ---------------------------------------------------------------- resident root cache (wire-format fused Verify)
+    def rootcache_config(self, slots: int) -> None:
+        """Empty the root cache and size it to `slots` (rounded up to a power of two; 0 = off)."""
+        _check(self.lib.hipbls_rootcache_config(slots), self.lib)
+
+    def rootcache_stats(self) -> Tuple[int, int, int, int]:
+        """(hits, misses, inserts, rollovers) since the last rootcache_config, summed over contexts."""
+        a, b, c, d = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self.lib.hipbls_rootcache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)),
+               self.lib)
+        return a.value, b.value, c.value, d.value
 
     # ---------------------------------------------------------------- pairing-check layout
     def set_pair_mode(self, mode: int) -> int:

@@ -324,6 +324,21 @@ int hipbls_hcache_prefetch(const uint8_t* msgs, const uint64_t* msg_offsets, uin
 int hipbls_keycache_config(uint64_t slots);
 int hipbls_keycache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts);
 
+/* Resident root cache used by the wire-format Verify batches that run one lane per item (hipbls_verify_batch[_device]
+ * above the lane-pair sizes, the submission queue's wire batches under HIPBLS_PAIR_SINGLE): a lookup kernel finds each
+ * 32-byte message in a per-context table in HBM, and on a hit the Verify kernel takes H(m) from the entry -- after
+ * comparing all 32 bytes and a check value -- instead of hashing the message to G2; a message it hashes is published
+ * once.  Messages of any other length bypass the cache.  Statuses are unchanged by the cache.  Entries are never
+ * replaced; when half the slots are written, the next call first waits for the device and empties the table (a
+ * rollover).  `slots` is rounded up to a power of two (256 B each, at most 2^22); 0 turns the cache off.  Default:
+ * 262,144 slots per context (64 MiB + 1 MiB), or HIPBLS_ROOTCACHE_SLOTS.  HIPBLS_ROOTCACHE_PARTITION=0 keeps the
+ * items in their own order instead of dealing the hits to the front.  hipbls_rootcache_config waits for the device
+ * and empties the cache and its counters; like hipbls_keycache_config it may run beside any other call.  Stats are
+ * summed over contexts, since the last config: eligible items found by the lookup, eligible items not found, entries
+ * written, rollovers.  hipbls_rootcache_stats waits for the device under each context's lock: a diagnostic. */
+int hipbls_rootcache_config(uint64_t slots);
+int hipbls_rootcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, uint64_t* rollovers);
+
 /* ------------------------------------------- device-resident variants (inputs already in HBM) ---- */
 /* Same semantics; every pointer is a device pointer; work is enqueued on `stream` (a hipStream_t,
  * NULL = the library's own non-blocking stream of that device, which is NOT ordered with the caller's default
