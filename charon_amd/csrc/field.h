@@ -52,6 +52,25 @@ extern thread_local uint64_t g_fp_sqr_count;
 #define BLS_COUNT_SQR() ((void)0)
 #endif
 
+// Host-only instrumentation (tests/native/sign_ct_host.cpp): every Fp / Fp2 product, squaring, addition, subtraction,
+// negation and inversion entry and every mask / select helper folds a one-byte operation code into a running digest,
+// in order.  Two runs with equal digests executed the same sequence of field operations and selects: the host-side
+// witness that a *_ct function's operation stream does not depend on its secret.  Undefined (every product build), the
+// hooks compile to nothing.
+#if defined(BLS_CT_TRACE) && !defined(__HIP_DEVICE_COMPILE__)
+namespace bls {
+extern thread_local uint64_t g_ct_trace;
+enum : uint8_t {
+  CT_FP_MUL = 1, CT_FP_SQR, CT_FP_ADD, CT_FP_SUB, CT_FP_NEG, CT_FP_INV,
+  CT_FP2_MUL, CT_FP2_SQR, CT_FP2_ADD, CT_FP2_SUB, CT_FP2_NEG, CT_FP2_INV,
+  CT_SEL_BFI, CT_MASK_BIT0, CT_MASK_EQ
+};
+}  // namespace bls
+#define BLS_CT_OP(code) (::bls::g_ct_trace = (::bls::g_ct_trace ^ (uint64_t)(code)) * 0x100000001b3ull)
+#else
+#define BLS_CT_OP(code) ((void)0)
+#endif
+
 // Test build (tests/test_operand_contract.py, host only): the device routines' operand contracts checked wherever the
 // host runs the same per-lane code.  The product routines take operands below 2^382 (their carry elision, tools/
 // gen_fp_asm.py _comba; every operand is canonical or a lazy sum below 2p), the Fp2 square and the modular add / sub
@@ -152,6 +171,7 @@ BLS_HD BLS_INLINE void fp_sub(fp& r, const fp& a, const fp& b) {
 #else
 // r = a + b mod p
 BLS_HD BLS_INLINE void fp_add(fp& r, const fp& a, const fp& b) {
+  BLS_CT_OP(CT_FP_ADD);
   BLS_CONTRACT(fp_canonical(a) && fp_canonical(b), "fp_add: an operand is not canonical");
   uint32_t s[12];
   uint64_t c = 0;
@@ -177,6 +197,7 @@ BLS_HD BLS_INLINE void fp_add(fp& r, const fp& a, const fp& b) {
 
 // r = a - b mod p
 BLS_HD BLS_INLINE void fp_sub(fp& r, const fp& a, const fp& b) {
+  BLS_CT_OP(CT_FP_SUB);
   BLS_CONTRACT(fp_canonical(a) && fp_canonical(b), "fp_sub: an operand is not canonical");
   uint32_t d[12];
   int64_t br = 0;
@@ -223,6 +244,7 @@ BLS_HD BLS_INLINE void fp_neg(fp& r, const fp& a) {
 }
 #else
 BLS_HD BLS_INLINE void fp_neg(fp& r, const fp& a) {
+  BLS_CT_OP(CT_FP_NEG);
   fp z;
   fp_set_zero(z);
   fp_sub(r, z, a);
@@ -465,6 +487,7 @@ static inline void fp_mul_impl64(fp& r, const fp& a, const fp& b) {
 #endif
 BLS_HD BLS_NOINLINE fp fp_mul_v(fp a, fp b) {
   BLS_COUNT_MUL();
+  BLS_CT_OP(CT_FP_MUL);
 #if defined(BLS_CONTRACT_CHECK)
   BLS_CONTRACT(fp_product_operand(a) && fp_product_operand(b), "fp_mul: an operand is not below 2p and 2^382");
   g_contract_lazy_operands += !fp_canonical(a) || !fp_canonical(b);
@@ -481,6 +504,7 @@ BLS_HD BLS_NOINLINE fp fp_mul_v(fp a, fp b) {
 }
 BLS_HD BLS_NOINLINE fp fp_sqr_v(fp a) {
   BLS_COUNT_SQR();
+  BLS_CT_OP(CT_FP_SQR);
 #if defined(BLS_CONTRACT_CHECK)
   BLS_CONTRACT(fp_product_operand(a), "fp_sqr: the operand is not below 2p and 2^382");
   fp_reduce_2p(a, a);
@@ -657,10 +681,17 @@ BLS_HD BLS_INLINE uint32_t bfi(uint32_t m, uint32_t a, uint32_t b) {  // m ? a :
   return r;
 }
 #else
-BLS_HD BLS_INLINE uint32_t mask_bit0(uint32_t x) { return 0u - (x & 1u); }
-BLS_HD BLS_INLINE uint32_t bfi(uint32_t m, uint32_t a, uint32_t b) { return (m & a) | (~m & b); }
+BLS_HD BLS_INLINE uint32_t mask_bit0(uint32_t x) {
+  BLS_CT_OP(CT_MASK_BIT0);
+  return 0u - (x & 1u);
+}
+BLS_HD BLS_INLINE uint32_t bfi(uint32_t m, uint32_t a, uint32_t b) {
+  BLS_CT_OP(CT_SEL_BFI);
+  return (m & a) | (~m & b);
+}
 #endif
 BLS_HD BLS_INLINE uint32_t mask_eq(uint32_t a, uint32_t b) {  // all ones if a == b (a ^ b < 2^31)
+  BLS_CT_OP(CT_MASK_EQ);
   return (uint32_t)((int32_t)((a ^ b) - 1u) >> 31);
 }
 
@@ -809,6 +840,7 @@ BLS_HD BLS_INLINE void lin_mod(int32_t* r, const int32_t* u, const int32_t* v, i
 }  // namespace gcd30
 
 BLS_HD BLS_CALL void fp_inv(fp& r, const fp& a_in) {
+  BLS_CT_OP(CT_FP_INV);
   using namespace gcd30;
   int32_t a[13], b[13], u[13], v[13];
   to30(a, a_in.v);

@@ -62,6 +62,13 @@ __global__ void k_rlcb_items(uint64_t n, const uint8_t* pks, const uint8_t* sigs
                              bls::keycache kc);
 }
 
+// Secret-independent Sign and SecretToPublicKey (sign_ct.hip: its own translation unit, C linkage).
+extern "C" {
+__global__ void k_sign_ct_hash(const uint8_t* msgs, const uint64_t* offs, uint64_t n, uint32_t* H);
+__global__ void k_sign_ct_mul(const uint8_t* sks, const uint32_t* H, uint64_t n, uint8_t* out, int32_t* status);
+__global__ void k_sk_to_pk_ct(const uint8_t* sks, uint64_t n, uint8_t* out, int32_t* status);
+}
+
 // The eight-lane latency path (verify_lat.hip, its own translation unit: BLS_FP2_PAIR build in namespace bls_fp2p).
 namespace bls_fp2p {
 __global__ void k_verify_prep8(const uint8_t* pks, const uint8_t* msgs, const uint64_t* offs, const uint8_t* sigs,
@@ -284,6 +291,7 @@ struct Context {
   DevBuf fk_h, fk_hcol, fk_mlist;
   DevBuf fk_slices, fk_poff, fk_parts, fk_pflags;  // its split key sum: slice plan, partial sums and their flags
   DevBuf v_ws;                                                             // lane-pair Verify points (SoA)
+  DevBuf ct_h;  // the secret-independent Sign's H(m) (Jacobian SoA, 72 words per item; public data)
   // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
   // the call's own H(m) table and its prep + check workspace; used under the lock up to the call's stream sync
   DevBuf vk_midx, vk_slot, vk_mlist, vk_h, vk_ws;
@@ -556,6 +564,7 @@ const KernelRef kKernels[] = {
     KREF(k_verify_gather_keys), KREF8(k_verify_prep8_keys), KREF8(k_hcache_fill8),
     KREF(k_fav_batch_keys), KREF16W(k_fav_pair_lq16_keys), KREF(k_fav_sum_keys),
     KREF(k_root_lookup),
+    KREF(k_sign_ct_hash), KREF(k_sign_ct_mul), KREF(k_sk_to_pk_ct),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -3015,6 +3024,76 @@ int sk_to_pk_host(Context& c, const uint8_t* sks, uint64_t n, uint8_t* out_pks, 
   return HIPBLS_OK;
 }
 
+// Secret-independent Sign (sign_ct.hip): the hash of the public messages into the workspace, then the one kernel that
+// sees the secrets.  Ordered against the workspace's previous user on any stream (ws_begin / ws_end).
+int launch_sign_ct(Context& c, const uint8_t* d_sks, const uint8_t* d_msgs, const uint64_t* d_offs, uint64_t n,
+                   uint8_t* d_out, int32_t* d_status, hipStream_t s) {
+  HIP_TRY(c.ct_h.ensure(n * 72 * 4));
+  int rc = ws_begin(c, s);
+  if (rc) return rc;
+  uint32_t* const H = (uint32_t*)c.ct_h.p;
+  rc = timed(c, "sign_ct_hash", s, [&] {
+    hipLaunchKernelGGL(k_sign_ct_hash, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_msgs, d_offs, n, H);
+  });
+  if (rc) return rc;
+  rc = timed(c, "sign_ct_mul", s, [&] {
+    hipLaunchKernelGGL(k_sign_ct_mul, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_sks, (const uint32_t*)H, n,
+                       d_out, d_status);
+  });
+  if (rc) return rc;
+  return ws_end(c, s);
+}
+
+int launch_sk_to_pk_ct(Context& c, const uint8_t* d_sks, uint64_t n, uint8_t* d_out, int32_t* d_status,
+                       hipStream_t s) {
+  return timed(c, "sk_to_pk_ct", s, [&] {
+    hipLaunchKernelGGL(k_sk_to_pk_ct, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_sks, n, d_out, d_status);
+  });
+}
+
+// sign_host / sk_to_pk_host over the secret-independent kernels.  The device copy of the secrets is zeroed on the
+// call's stream before the call returns (the staging buffer is reused by later calls of every kind).
+int sign_ct_host(Context& c, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs, uint64_t n,
+                 uint8_t* out_sigs, int32_t* status) {
+  const uint64_t msg_total = offs[n];
+  HIP_TRY(c.b_pk.ensure(n * 32));
+  HIP_TRY(c.b_msg.ensure(msg_total ? msg_total : 1));
+  HIP_TRY(c.b_off.ensure((n + 1) * 8));
+  HIP_TRY(c.b_out.ensure(n * 96));
+  HIP_TRY(c.b_st.ensure(n * 4));
+  HIP_TRY(hipMemcpyAsync(c.b_pk.p, sks, n * 32, hipMemcpyHostToDevice, c.stream));
+  if (msg_total) HIP_TRY(hipMemcpyAsync(c.b_msg.p, msgs, msg_total, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipMemcpyAsync(c.b_off.p, offs, (n + 1) * 8, hipMemcpyHostToDevice, c.stream));
+  const int rc = launch_sign_ct(c, (const uint8_t*)c.b_pk.p, (const uint8_t*)c.b_msg.p, (const uint64_t*)c.b_off.p, n,
+                                (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p, c.stream);
+  HIP_TRY(hipMemsetAsync(c.b_pk.p, 0, n * 32, c.stream));  // also after a failed launch
+  if (rc) {
+    (void)hipStreamSynchronize(c.stream);
+    return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out_sigs, c.b_out.p, n * 96, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  return HIPBLS_OK;
+}
+
+int sk_to_pk_ct_host(Context& c, const uint8_t* sks, uint64_t n, uint8_t* out_pks, int32_t* status) {
+  HIP_TRY(c.b_pk.ensure(n * 32));
+  HIP_TRY(c.b_out.ensure(n * 48));
+  HIP_TRY(c.b_st.ensure(n * 4));
+  HIP_TRY(hipMemcpyAsync(c.b_pk.p, sks, n * 32, hipMemcpyHostToDevice, c.stream));
+  const int rc = launch_sk_to_pk_ct(c, (const uint8_t*)c.b_pk.p, n, (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p, c.stream);
+  HIP_TRY(hipMemsetAsync(c.b_pk.p, 0, n * 32, c.stream));  // also after a failed launch
+  if (rc) {
+    (void)hipStreamSynchronize(c.stream);
+    return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out_pks, c.b_out.p, n * 48, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  return HIPBLS_OK;
+}
+
 int fav_host(Context& c, const uint8_t* pks, const uint64_t* koffs, uint64_t n_groups, const uint8_t* sigs,
              const uint8_t* msgs, const uint64_t* moffs, int32_t* status) {
   const uint64_t nkeys = koffs[n_groups], msg_total = moffs[n_groups];
@@ -3664,6 +3743,50 @@ int hipbls_secret_to_public_key_batch_device(const uint8_t* d_sks, uint64_t n, u
                      d_status);
   HIP_TRY(hipGetLastError());
   return HIPBLS_OK;
+}
+
+int hipbls_sign_batch_ct(const uint8_t* sks, const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t n,
+                         uint8_t* out_sigs, int32_t* status) {
+  if (n == 0) return HIPBLS_OK;
+  if (!sks || !msg_offsets || !out_sigs || !status || mul_overflows(n, 96)) return arg_err("bad sign arguments");
+  if (!offsets_ok(msg_offsets, n)) return arg_err("bad message offsets");
+  if (msg_offsets[n] && !msgs) return arg_err("null messages");
+  ENSURE_INIT();
+  return run_ranges(plan_ranges(n, parts_for(n, kSplitSign), nullptr), [&](Context& c, uint64_t lo, uint64_t hi) {
+    std::vector<uint64_t> tmp;
+    return sign_ct_host(c, sks + 32 * lo, msgs ? msgs + msg_offsets[lo] : msgs, rebase(msg_offsets, lo, hi, tmp),
+                        hi - lo, out_sigs + 96 * lo, status + lo);
+  });
+}
+
+int hipbls_sign_batch_ct_device(const uint8_t* d_sks, const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
+                                uint64_t n, uint8_t* d_out_sigs, int32_t* d_status, void* stream) {
+  if (n == 0) return HIPBLS_OK;
+  if (mul_overflows(n, 288)) return arg_err("too many items");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_sign_ct(c, d_sks, d_msgs, d_msg_offsets, n, d_out_sigs, d_status, s);
+}
+
+int hipbls_secret_to_public_key_batch_ct(const uint8_t* sks, uint64_t n, uint8_t* out_pks, int32_t* status) {
+  if (n == 0) return HIPBLS_OK;
+  if (!sks || !out_pks || !status || mul_overflows(n, 48)) return arg_err("bad arguments");
+  ENSURE_INIT();
+  return run_ranges(plan_ranges(n, parts_for(n, kSplitSign), nullptr), [&](Context& c, uint64_t lo, uint64_t hi) {
+    return sk_to_pk_ct_host(c, sks + 32 * lo, hi - lo, out_pks + 48 * lo, status + lo);
+  });
+}
+
+int hipbls_secret_to_public_key_batch_ct_device(const uint8_t* d_sks, uint64_t n, uint8_t* d_out_pks,
+                                                int32_t* d_status, void* stream) {
+  if (n == 0) return HIPBLS_OK;
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_sk_to_pk_ct(c, d_sks, n, d_out_pks, d_status, s);
 }
 
 int hipbls_verify_aggregate_batch(const uint8_t* pks, const uint64_t* key_offsets, uint64_t n_groups,

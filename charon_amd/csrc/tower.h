@@ -37,14 +37,17 @@ BLS_HD BLS_INLINE void fp2_set_one(fp2& r) {
 BLS_HD BLS_INLINE bool fp2_is_zero(const fp2& a) { return fp_is_zero(a.c0) && fp_is_zero(a.c1); }
 BLS_HD BLS_INLINE bool fp2_eq(const fp2& a, const fp2& b) { return fp_eq(a.c0, b.c0) && fp_eq(a.c1, b.c1); }
 BLS_HD BLS_INLINE void fp2_add(fp2& r, const fp2& a, const fp2& b) {
+  BLS_CT_OP(CT_FP2_ADD);
   fp_add(r.c0, a.c0, b.c0);
   fp_add(r.c1, a.c1, b.c1);
 }
 BLS_HD BLS_INLINE void fp2_sub(fp2& r, const fp2& a, const fp2& b) {
+  BLS_CT_OP(CT_FP2_SUB);
   fp_sub(r.c0, a.c0, b.c0);
   fp_sub(r.c1, a.c1, b.c1);
 }
 BLS_HD BLS_INLINE void fp2_neg(fp2& r, const fp2& a) {
+  BLS_CT_OP(CT_FP2_NEG);
   fp_neg(r.c0, a.c0);
   fp_neg(r.c1, a.c1);
 }
@@ -207,6 +210,7 @@ BLS_HD BLS_INLINE void fp2_mul(fp2& r, const fp2& a, const fp2& b) {
 }
 #else
 BLS_HD BLS_INLINE void fp2_mul(fp2& r, const fp2& a_in, const fp2& b_in) {
+  BLS_CT_OP(CT_FP2_MUL);
   // Karatsuba: 3 Fp products; the two sums only feed the third product, so they stay unreduced (fp_add_lazy)
 #if defined(BLS_CONTRACT_CHECK)
   // the device routine's operands: below 2^382 each, and 2p - b1 formed inside it (b1 <= 2p)
@@ -303,6 +307,7 @@ BLS_HD BLS_INLINE void fp2_sqr(fp2& r, const fp2& a) {
 }
 #else
 BLS_HD BLS_INLINE void fp2_sqr(fp2& r, const fp2& a) {
+  BLS_CT_OP(CT_FP2_SQR);
   // the device routine forms (a0 + a1), (a0 + p - a1) and 2 a1 inside it: canonical operands only
   BLS_CONTRACT(fp_canonical(a.c0) && fp_canonical(a.c1), "fp2_sqr: an operand is not canonical");
   fp2_sqr_c(r, a);
@@ -318,6 +323,7 @@ BLS_HD BLS_INLINE void fp2_sqr(fp2& r, const fp2& a) {
 #endif
 #endif
 BLS_HD BLS_CALL void fp2_inv(fp2& r, const fp2& a_in) {
+  BLS_CT_OP(CT_FP2_INV);
   const fp2 a = a_in;
   fp t0, t1;
   fp_sqr(t0, a.c0);

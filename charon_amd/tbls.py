@@ -113,6 +113,10 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_threshold_aggregate_batch_device": ([vp, vp, vp, u64, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_sign_batch_device": ([vp, vp, vp, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_secret_to_public_key_batch_device": ([vp, u64, vp, vp, vp], ctypes.c_int),
+        "hipbls_sign_batch_ct": ([u8p, u8p, u64p, u64, u8p, i32p], ctypes.c_int),
+        "hipbls_secret_to_public_key_batch_ct": ([u8p, u64, u8p, i32p], ctypes.c_int),
+        "hipbls_sign_batch_ct_device": ([vp, vp, vp, u64, vp, vp, vp], ctypes.c_int),
+        "hipbls_secret_to_public_key_batch_ct_device": ([vp, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_batch_verify_rlc": ([u8p, u8p, u32p, u64, u8p, u64p, u64, u8p, i32p], ctypes.c_int),
         "hipbls_batch_verify_rlc_device": ([vp, vp, vp, u64, vp, vp, u64, u8p, vp, vp], ctypes.c_int),
         "hipbls_rlc_stats": ([u64p, u64p, u64p], ctypes.c_int),
@@ -167,6 +171,8 @@ def exported_symbols() -> List[str]:
         "hipbls_keycache_config", "hipbls_keycache_stats", "hipbls_hcache_prefetch",
         "hipbls_verify_aggregate_batch_keys", "hipbls_verify_aggregate_batch_keys_device",
         "hipbls_rootcache_config", "hipbls_rootcache_stats",
+        "hipbls_sign_batch_ct", "hipbls_secret_to_public_key_batch_ct", "hipbls_sign_batch_ct_device",
+        "hipbls_secret_to_public_key_batch_ct_device",
     ]
 
 
@@ -261,7 +267,8 @@ class HipBLS:
         raise TBLSError("cannot generate insecure key")
 
     def secret_to_public_key(self, secret: bytes) -> bytes:
-        pk, st = self.secret_to_public_key_batch([secret])
+        """herumi.go:67-80, on the secret-independent kernel: this is the call real secrets take."""
+        pk, st = self.secret_to_public_key_batch_ct([secret])
         if st[0] != OK:
             v = int.from_bytes(secret, "big")
             if v >= R:
@@ -276,6 +283,17 @@ class HipBLS:
         st = _status_array(n)
         _check(self.lib.hipbls_secret_to_public_key_batch(b"".join(secrets_), n, out, st), self.lib)
         raw = out.raw  # one copy: .raw rebuilds the bytes object on every access
+        return [raw[48 * i:48 * i + 48] for i in range(n)], list(st)[:n]
+
+    def secret_to_public_key_batch_ct(self, secrets_: Sequence[bytes]) -> Tuple[List[bytes], List[int]]:
+        """secret_to_public_key_batch by the secret-independent kernel (hipbls_secret_to_public_key_batch_ct): same
+        bytes and statuses; the instruction stream and the memory addresses do not depend on the secrets."""
+        n = len(secrets_)
+        _check_lengths("secret keys", secrets_, 32)
+        out = ctypes.create_string_buffer(48 * max(n, 1))
+        st = _status_array(n)
+        _check(self.lib.hipbls_secret_to_public_key_batch_ct(b"".join(secrets_), n, out, st), self.lib)
+        raw = out.raw
         return [raw[48 * i:48 * i + 48] for i in range(n)], list(st)[:n]
 
     def _split(self, secret: bytes, total: int, threshold: int, tail: Sequence[bytes]) -> Dict[int, bytes]:
@@ -316,7 +334,8 @@ class HipBLS:
 
     # ---------------------------------------------------------------- hot path
     def sign(self, private_key: bytes, data: bytes) -> bytes:
-        sigs, st = self.sign_batch([private_key], [data])
+        """herumi.go:303-313, on the secret-independent kernels: this is the call real secrets take."""
+        sigs, st = self.sign_batch_ct([private_key], [data])
         if st[0] != OK:
             raise TBLSError("cannot unmarshal secret into Herumi secret key")
         return sigs[0]
@@ -330,6 +349,20 @@ class HipBLS:
         out = ctypes.create_string_buffer(96 * max(n, 1))
         st = _status_array(n)
         _check(self.lib.hipbls_sign_batch(b"".join(sks), blob, offs, n, out, st), self.lib)
+        raw = out.raw
+        return [raw[96 * i:96 * i + 96] for i in range(n)], list(st)[:n]
+
+    def sign_batch_ct(self, sks: Sequence[bytes], msgs: Sequence[bytes]) -> Tuple[List[bytes], List[int]]:
+        """sign_batch by the secret-independent kernels (hipbls_sign_batch_ct): same bytes and statuses; sign_batch
+        stays the variable-time generator for test and benchmark data."""
+        n = len(sks)
+        if len(msgs) != n:
+            raise ValueError("mismatching lengths")
+        _check_lengths("secret keys", sks, 32)
+        blob, offs = _offsets(msgs)
+        out = ctypes.create_string_buffer(96 * max(n, 1))
+        st = _status_array(n)
+        _check(self.lib.hipbls_sign_batch_ct(b"".join(sks), blob, offs, n, out, st), self.lib)
         raw = out.raw
         return [raw[96 * i:96 * i + 96] for i in range(n)], list(st)[:n]
 

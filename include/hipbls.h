@@ -20,6 +20,7 @@
  *   hipbls_threshold_aggregate_batch   tbls.Implementation.ThresholdAggregate tbls/tbls.go:50-51, tbls/herumi.go:244-283
  *   hipbls_sign_batch                  tbls.Implementation.Sign              tbls/tbls.go:57-59, tbls/herumi.go:303-313
  *   hipbls_secret_to_public_key_batch  tbls.Implementation.SecretToPublicKey tbls/tbls.go:36-38, tbls/herumi.go:67-80
+ *   hipbls_sign_batch_ct, hipbls_secret_to_public_key_batch_ct: the same two for real secrets, secret-independent
  *   hipbls_verify_aggregate[_batch]    tbls.Implementation.VerifyAggregate   tbls/tbls.go:61-63, tbls/herumi.go:315-339
  *   hipbls_aggregate                   tbls.Implementation.Aggregate         tbls/tbls.go:65-67, tbls/herumi.go:220-242
  *   hipbls_threshold_split             tbls.Implementation.ThresholdSplit[Insecure] tbls/tbls.go:40-47, tbls/herumi.go:84-181
@@ -187,6 +188,22 @@ int hipbls_sign_batch(const uint8_t* sks, const uint8_t* msgs, const uint64_t* m
 
 /* out_pks[48 i ..] = sks[32 i ..] * g1.  status[i] = OK | ERR_SECRET (zero or >= r). */
 int hipbls_secret_to_public_key_batch(const uint8_t* sks, uint64_t n, uint8_t* out_pks, int32_t* status);
+
+/* hipbls_sign_batch for real secrets (tbls.Implementation.Sign, tbls/herumi.go:303-313): same arguments, bytes,
+ * statuses and argument errors, computed by kernels whose instruction stream and memory addresses do not depend on
+ * sks.  The public messages are hashed by one kernel (timed as sign_ct_hash); the only kernel that
+ * reads the secrets (sign_ct_mul) computes [sk] H(m) with 64 x (double, full scan of a 16-entry table, unconditional
+ * addition, select by mask) and compresses with the sign flag and the infinity encoding chosen by mask.  A secret
+ * >= r runs the same stream and yields ERR_SECRET with a zero-filled output.  The device copy of sks is zeroed on the
+ * call's stream before the call returns.  hipbls_sign_batch stays the variable-time generator for test and bench
+ * data. */
+int hipbls_sign_batch_ct(const uint8_t* sks, const uint8_t* msgs, const uint64_t* msg_offsets, uint64_t n,
+                         uint8_t* out_sigs, int32_t* status);
+
+/* hipbls_secret_to_public_key_batch for real secrets (tbls.Implementation.SecretToPublicKey, tbls/herumi.go:67-80):
+ * same arguments, bytes and statuses (ERR_SECRET for zero or >= r), by a fixed 4-bit window over [0..15] g1 read by a
+ * full scan (kernel timed as sk_to_pk_ct).  The device copy of sks is zeroed before the call returns. */
+int hipbls_secret_to_public_key_batch_ct(const uint8_t* sks, uint64_t n, uint8_t* out_pks, int32_t* status);
 
 /* FastAggregateVerify(pks[0..n), sig, msg).  *status = OK | ERR_PUBKEY | ERR_SIGNATURE | ERR_VERIFY. */
 int hipbls_verify_aggregate(const uint8_t* pks, uint64_t n, const uint8_t* sig, const uint8_t* msg,
@@ -401,6 +418,12 @@ int hipbls_sign_batch_device(const uint8_t* d_sks, const uint8_t* d_msgs, const 
                              uint64_t n, uint8_t* d_out_sigs, int32_t* d_status, void* stream);
 int hipbls_secret_to_public_key_batch_device(const uint8_t* d_sks, uint64_t n, uint8_t* d_out_pks,
                                              int32_t* d_status, void* stream);
+/* Device variants of hipbls_sign_batch_ct / hipbls_secret_to_public_key_batch_ct (tbls/herumi.go:303-313, 67-80):
+ * they only enqueue.  The secrets stay in the caller's buffer; clearing it is the caller's. */
+int hipbls_sign_batch_ct_device(const uint8_t* d_sks, const uint8_t* d_msgs, const uint64_t* d_msg_offsets,
+                                uint64_t n, uint8_t* d_out_sigs, int32_t* d_status, void* stream);
+int hipbls_secret_to_public_key_batch_ct_device(const uint8_t* d_sks, uint64_t n, uint8_t* d_out_pks,
+                                                int32_t* d_status, void* stream);
 
 /* As hipbls_batch_verify_rlc; seed32 is a host pointer.  An out-of-range msg_idx[i] yields
  * status[i] = HIPBLS_ERR_ARG. */

@@ -329,14 +329,15 @@ func (HipBLS) GenerateInsecureKey(t *testing.T, random io.Reader) (tbls.PrivateK
 	return tbls.PrivateKey{}, errors.New("cannot generate insecure key")
 }
 
-// SecretToPublicKey (tbls/herumi.go:67-80).
+// SecretToPublicKey (tbls/herumi.go:67-80), on the secret-independent kernel (hipbls_secret_to_public_key_batch_ct):
+// the instruction stream and the memory addresses of the device code do not depend on the secret.
 func (HipBLS) SecretToPublicKey(secret tbls.PrivateKey) (tbls.PublicKey, error) {
 	if !validScalar(secret) {
 		return tbls.PublicKey{}, errors.New("cannot unmarshal secret into Herumi secret key")
 	}
 	var pk tbls.PublicKey
 	status := make([]int32, 1)
-	if rc := C.hipbls_secret_to_public_key_batch(u8(secret[:]), 1, u8(pk[:]), i32(status)); rc != C.HIPBLS_OK {
+	if rc := C.hipbls_secret_to_public_key_batch_ct(u8(secret[:]), 1, u8(pk[:]), i32(status)); rc != C.HIPBLS_OK {
 		return tbls.PublicKey{}, devErr(rc)
 	}
 	if status[0] != C.HIPBLS_OK { // zero secret: GetSafePublicKey fails (herumi.go:74)
@@ -415,7 +416,8 @@ func (HipBLS) RecoverSecret(shares map[int]tbls.PrivateKey, _, _ uint) (tbls.Pri
 
 // ---------------------------------------------------------------- hot path
 
-// Sign (tbls/herumi.go:303-313).
+// Sign (tbls/herumi.go:303-313), on the secret-independent kernels (hipbls_sign_batch_ct): the message is hashed by
+// one kernel, and the only kernel that reads the key runs one instruction stream whatever the key's bits.
 func (HipBLS) Sign(privateKey tbls.PrivateKey, data []byte) (tbls.Signature, error) {
 	if !validScalar(privateKey) {
 		return tbls.Signature{}, errors.New("cannot unmarshal secret into Herumi secret key")
@@ -423,7 +425,7 @@ func (HipBLS) Sign(privateKey tbls.PrivateKey, data []byte) (tbls.Signature, err
 	var sig tbls.Signature
 	flat, offs := flatten([][]byte{data})
 	status := make([]int32, 1)
-	if rc := C.hipbls_sign_batch(u8(privateKey[:]), u8(flat), u64(offs), 1, u8(sig[:]), i32(status)); rc != C.HIPBLS_OK {
+	if rc := C.hipbls_sign_batch_ct(u8(privateKey[:]), u8(flat), u64(offs), 1, u8(sig[:]), i32(status)); rc != C.HIPBLS_OK {
 		return tbls.Signature{}, devErr(rc)
 	}
 	if status[0] != C.HIPBLS_OK {
