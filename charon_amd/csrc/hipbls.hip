@@ -69,6 +69,19 @@ __global__ void k_sign_ct_mul(const uint8_t* sks, const uint32_t* H, uint64_t n,
 __global__ void k_sk_to_pk_ct(const uint8_t* sks, uint64_t n, uint8_t* out, int32_t* status);
 }
 
+// Secret-independent ThresholdSplit / RecoverSecret in batches (deal_ct.hip: its own translation unit, C linkage;
+// DESIGN.md 4.13).
+extern "C" {
+__global__ void k_g1_comb_build(uint32_t* T);
+__global__ void k_deal_ct(const uint8_t* secrets, const uint8_t* tails, uint32_t n, uint32_t total, uint32_t threshold,
+                          const uint32_t* T, uint8_t* out_shares, int32_t* status, uint8_t* out_pubs,
+                          int32_t* pub_status, uint8_t* sink);
+__global__ void k_recover_plan(const uint64_t* offs, uint32_t n_groups, uint32_t* m_max);
+__global__ void k_recover_ct(const uint8_t* shares, const int64_t* ids, const uint64_t* offs, uint32_t n_groups,
+                             uint32_t n_parts, const uint32_t* m_max, const uint32_t* T, uint8_t* out_secrets,
+                             int32_t* status, uint8_t* out_pubkeys, int32_t* pk_status, uint8_t* sink);
+}
+
 // The eight-lane latency path (verify_lat.hip, its own translation unit: BLS_FP2_PAIR build in namespace bls_fp2p).
 namespace bls_fp2p {
 __global__ void k_verify_prep8(const uint8_t* pks, const uint8_t* msgs, const uint64_t* offs, const uint8_t* sigs,
@@ -292,6 +305,12 @@ struct Context {
   DevBuf fk_slices, fk_poff, fk_parts, fk_pflags;  // its split key sum: slice plan, partial sums and their flags
   DevBuf v_ws;                                                             // lane-pair Verify points (SoA)
   DevBuf ct_h;  // the secret-independent Sign's H(m) (Jacobian SoA, 72 words per item; public data)
+  // The batched split / recover (deal_ct.hip): the fixed-base comb [j 16^w] g1 (public; built at first use), the
+  // 64-byte sink that lanes without a store write zeros to, the recover launch's largest group size, and the host
+  // calls' public-key outputs.
+  DevBuf ct_comb, ct_sink, ct_plan, dl_pub, dl_pst;
+  int comb_state = 0;  // 0: not built, 1: build enqueued (comb_ev recorded behind it), 2: seen complete
+  hipEvent_t comb_ev = nullptr;
   // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
   // the call's own H(m) table and its prep + check workspace; used under the lock up to the call's stream sync
   DevBuf vk_midx, vk_slot, vk_mlist, vk_h, vk_ws;
@@ -550,10 +569,10 @@ const KernelRef kKernels[] = {
     KREF(k_g1m_hist), KREF(k_g1m_plan), KREF(k_g1m_rank), KREF(k_g1m_run), KREF(k_g1m_scatter), KREF(k_g2_decode),
     KREF(k_g2_sum_final), KREF(k_g2_sum_partial), KREF(k_msm_fix), KREF(k_msm_hist), KREF(k_msm_run), KREF(k_msm_scan),
     KREF(k_msm_scatter), KREF(k_msm_segment), KREF(k_msm_window), KREF(k_msm_wsum), KREF(k_pubtab_load),
-    KREF(k_recover_secret), KREF(k_rlc_fallback), KREF(k_rlc_fallback_lg2), KREF(k_rlc_hash), KREF(k_rlc_items),
+    KREF(k_rlc_fallback), KREF(k_rlc_fallback_lg2), KREF(k_rlc_hash), KREF(k_rlc_items),
     KREF(k_rlc_window), KREF(k_rlc_window_lg2), KREF(k_rlcb_chunks), KREF(k_rlcb_items), KREF(k_rlcb_mark),
     KREF(k_scan_apply), KREF(k_scan_part), KREF(k_scan_top), KREF(k_sign), KREF(k_signing_roots), KREF(k_sk_to_pk),
-    KREF(k_tagg_scale), KREF(k_tagg_sum), KREF(k_tagg_sum_s), KREF(k_tagg_unscale), KREF(k_threshold_split),
+    KREF(k_tagg_scale), KREF(k_tagg_sum), KREF(k_tagg_sum_s), KREF(k_tagg_unscale),
     KREF(k_tv_check_unscale), KREF(k_tv_join), KREF(k_tv_phase_a), KREF(k_tv_prep_pk), KREF(k_tv_prep_pk2),
     KREF(k_verify_fused), KREF(k_verify_keys), KREF(k_verify_pair_lg2), KREF(k_verify_pair_lq4),
     KREF(k_verify_pair_single), KREF(k_verify_prep), KREF(k_zero_sig_status), KREF8(k_g1m_miller8),
@@ -565,6 +584,7 @@ const KernelRef kKernels[] = {
     KREF(k_fav_batch_keys), KREF16W(k_fav_pair_lq16_keys), KREF(k_fav_sum_keys),
     KREF(k_root_lookup),
     KREF(k_sign_ct_hash), KREF(k_sign_ct_mul), KREF(k_sk_to_pk_ct),
+    KREF(k_g1_comb_build), KREF(k_deal_ct), KREF(k_recover_plan), KREF(k_recover_ct),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -3094,6 +3114,165 @@ int sk_to_pk_ct_host(Context& c, const uint8_t* sks, uint64_t n, uint8_t* out_pk
   return HIPBLS_OK;
 }
 
+// ---- ThresholdSplit / RecoverSecret in batches on the secret-independent kernels (deal_ct.hip) ----
+constexpr size_t kCombBytes = 64 * 15 * 24 * 4;  // deal_ct.h COMB_WORDS
+
+// The context's comb table, built on the library stream by the first call that needs it.  No host wait: until the
+// build's event has completed, every call's stream is ordered behind it (a stream wait); from then on a call finds
+// the table complete and does nothing here, so a later call may also sit on a capturing stream.
+int ensure_comb(Context& c, hipStream_t s) {
+  if (c.comb_state == 2) return HIPBLS_OK;
+  if (c.comb_state == 0) {
+    HIP_TRY(c.ct_comb.ensure(kCombBytes));
+    HIP_TRY(c.ct_sink.ensure(64));
+    HIP_TRY(c.ct_plan.ensure(4));
+    if (!c.comb_ev) HIP_TRY(hipEventCreateWithFlags(&c.comb_ev, hipEventDisableTiming));
+    const int rc = timed(c, "g1_comb_build", c.stream, [&] {
+      hipLaunchKernelGGL(k_g1_comb_build, dim3((unsigned)grid_for(64 * 15)), dim3(kBlock), 0, c.stream,
+                         (uint32_t*)c.ct_comb.p);
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c.comb_ev, c.stream));
+    c.comb_state = 1;
+  }
+  if (hipEventQuery(c.comb_ev) == hipSuccess) {
+    c.comb_state = 2;
+    return HIPBLS_OK;
+  }
+  (void)hipGetLastError();  // hipErrorNotReady
+  if (s != c.stream) HIP_TRY(hipStreamWaitEvent(s, c.comb_ev, 0));
+  return HIPBLS_OK;
+}
+
+// n_val >= 1 validators, n_val (total + 1) lanes below 2^31.  d_pubs / d_pst both null or both given.
+int launch_deal_ct(Context& c, const uint8_t* d_secrets, const uint8_t* d_tails, uint64_t n_val, uint32_t total,
+                   uint32_t threshold, uint8_t* d_shares, int32_t* d_status, uint8_t* d_pubs, int32_t* d_pst,
+                   hipStream_t s) {
+  int rc = ensure_comb(c, s);
+  if (rc) return rc;
+  const uint32_t n = (uint32_t)(n_val * ((uint64_t)total + 1));
+  return timed(c, "deal_ct", s, [&] {
+    hipLaunchKernelGGL(k_deal_ct, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_secrets, d_tails, n, total,
+                       threshold, (const uint32_t*)c.ct_comb.p, d_shares, d_status, d_pubs, d_pst,
+                       (uint8_t*)c.ct_sink.p);
+  });
+}
+
+// n_groups >= 1 groups over n_parts shares, both below 2^31.  The largest group size goes through ct_plan, which the
+// workspace ordering protects against a call on another stream.
+int launch_recover_ct(Context& c, const uint8_t* d_shares, const int64_t* d_ids, const uint64_t* d_offs,
+                      uint64_t n_groups, uint64_t n_parts, uint8_t* d_out, int32_t* d_status, uint8_t* d_pks,
+                      int32_t* d_pkst, hipStream_t s) {
+  int rc = ensure_comb(c, s);
+  if (rc) return rc;
+  rc = ws_begin(c, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(c.ct_plan.p, 0, 4, s));
+  hipLaunchKernelGGL(k_recover_plan, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, d_offs,
+                     (uint32_t)n_groups, (uint32_t*)c.ct_plan.p);
+  HIP_TRY(hipGetLastError());
+  rc = timed(c, "recover_ct", s, [&] {
+    hipLaunchKernelGGL(k_recover_ct, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, d_shares, d_ids, d_offs,
+                       (uint32_t)n_groups, (uint32_t)n_parts, (const uint32_t*)c.ct_plan.p,
+                       (const uint32_t*)c.ct_comb.p, d_out, d_status, d_pks, d_pkst, (uint8_t*)c.ct_sink.p);
+  });
+  if (rc) return rc;
+  return ws_end(c, s);
+}
+
+// The host forms.  Every device copy of a secret (root secrets, tails, shares in either direction, recovered secrets)
+// is zeroed on the call's stream before the call returns, whatever failed before: the copies in, the launch or the
+// copies out (wipe() runs on every path once the buffers exist, then the stream is drained).
+int deal_ct_host(Context& c, const uint8_t* secrets, const uint8_t* tails, uint64_t n_val, uint32_t total,
+                 uint32_t threshold, uint8_t* out_shares, int32_t* status, uint8_t* out_pubs, int32_t* pub_status) {
+  const uint64_t n = n_val * ((uint64_t)total + 1), tail_bytes = n_val * 32 * (uint64_t)(threshold - 1);
+  const uint64_t share_bytes = n_val * (uint64_t)total * 32;
+  HIP_TRY(c.b_pk.ensure(n_val * 32));
+  HIP_TRY(c.b_aux.ensure(tail_bytes ? tail_bytes : 1));
+  HIP_TRY(c.b_out.ensure(share_bytes));
+  HIP_TRY(c.b_st.ensure(n_val * 4));
+  if (out_pubs) {
+    HIP_TRY(c.dl_pub.ensure(n * 48));
+    HIP_TRY(c.dl_pst.ensure(n * 4));
+  }
+  auto body = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(c.b_pk.p, secrets, n_val * 32, hipMemcpyHostToDevice, c.stream));
+    if (tail_bytes) HIP_TRY(hipMemcpyAsync(c.b_aux.p, tails, tail_bytes, hipMemcpyHostToDevice, c.stream));
+    const int rc = launch_deal_ct(c, (const uint8_t*)c.b_pk.p, (const uint8_t*)c.b_aux.p, n_val, total, threshold,
+                                  (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p, out_pubs ? (uint8_t*)c.dl_pub.p : nullptr,
+                                  out_pubs ? (int32_t*)c.dl_pst.p : nullptr, c.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_shares, c.b_out.p, share_bytes, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_val * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out_pubs) {
+      HIP_TRY(hipMemcpyAsync(out_pubs, c.dl_pub.p, n * 48, hipMemcpyDeviceToHost, c.stream));
+      HIP_TRY(hipMemcpyAsync(pub_status, c.dl_pst.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+    }
+    return HIPBLS_OK;
+  };
+  const int rc = body();
+  const std::string err = g_last_error;
+  const hipError_t w1 = hipMemsetAsync(c.b_pk.p, 0, n_val * 32, c.stream);
+  const hipError_t w2 = tail_bytes ? hipMemsetAsync(c.b_aux.p, 0, tail_bytes, c.stream) : hipSuccess;
+  const hipError_t w3 = hipMemsetAsync(c.b_out.p, 0, share_bytes, c.stream);
+  const hipError_t sy = hipStreamSynchronize(c.stream);
+  if (rc) {
+    g_last_error = err;
+    return rc;
+  }
+  HIP_TRY(w1);
+  HIP_TRY(w2);
+  HIP_TRY(w3);
+  HIP_TRY(sy);
+  return HIPBLS_OK;
+}
+
+int recover_ct_host(Context& c, const uint8_t* shares, const int64_t* ids, const uint64_t* offs, uint64_t n_groups,
+                    uint8_t* out_secrets, int32_t* status, uint8_t* out_pks, int32_t* pk_status) {
+  const uint64_t n_parts = offs[n_groups];
+  HIP_TRY(c.b_aux.ensure(n_parts ? n_parts * 32 : 1));
+  HIP_TRY(c.b_ids.ensure(n_parts ? n_parts * 8 : 1));
+  HIP_TRY(c.b_off.ensure((n_groups + 1) * 8));
+  HIP_TRY(c.b_out.ensure(n_groups * 32));
+  HIP_TRY(c.b_st.ensure(n_groups * 4));
+  if (out_pks) {
+    HIP_TRY(c.dl_pub.ensure(n_groups * 48));
+    HIP_TRY(c.dl_pst.ensure(n_groups * 4));
+  }
+  auto body = [&]() -> int {
+    if (n_parts) {
+      HIP_TRY(hipMemcpyAsync(c.b_aux.p, shares, n_parts * 32, hipMemcpyHostToDevice, c.stream));
+      HIP_TRY(hipMemcpyAsync(c.b_ids.p, ids, n_parts * 8, hipMemcpyHostToDevice, c.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c.b_off.p, offs, (n_groups + 1) * 8, hipMemcpyHostToDevice, c.stream));
+    const int rc = launch_recover_ct(c, (const uint8_t*)c.b_aux.p, (const int64_t*)c.b_ids.p,
+                                     (const uint64_t*)c.b_off.p, n_groups, n_parts, (uint8_t*)c.b_out.p,
+                                     (int32_t*)c.b_st.p, out_pks ? (uint8_t*)c.dl_pub.p : nullptr,
+                                     out_pks ? (int32_t*)c.dl_pst.p : nullptr, c.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_secrets, c.b_out.p, n_groups * 32, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_groups * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out_pks) {
+      HIP_TRY(hipMemcpyAsync(out_pks, c.dl_pub.p, n_groups * 48, hipMemcpyDeviceToHost, c.stream));
+      HIP_TRY(hipMemcpyAsync(pk_status, c.dl_pst.p, n_groups * 4, hipMemcpyDeviceToHost, c.stream));
+    }
+    return HIPBLS_OK;
+  };
+  const int rc = body();
+  const std::string err = g_last_error;
+  const hipError_t w1 = n_parts ? hipMemsetAsync(c.b_aux.p, 0, n_parts * 32, c.stream) : hipSuccess;
+  const hipError_t w2 = hipMemsetAsync(c.b_out.p, 0, n_groups * 32, c.stream);
+  const hipError_t sy = hipStreamSynchronize(c.stream);
+  if (rc) {
+    g_last_error = err;
+    return rc;
+  }
+  HIP_TRY(w1);
+  HIP_TRY(w2);
+  HIP_TRY(sy);
+  return HIPBLS_OK;
+}
+
 int fav_host(Context& c, const uint8_t* pks, const uint64_t* koffs, uint64_t n_groups, const uint8_t* sigs,
              const uint8_t* msgs, const uint64_t* moffs, int32_t* status) {
   const uint64_t nkeys = koffs[n_groups], msg_total = moffs[n_groups];
@@ -3920,51 +4099,104 @@ int hipbls_aggregate_device(const uint8_t* d_sigs, uint64_t n, uint8_t* d_out_si
   return launch_aggregate(c, d_sigs, n, d_out_sig, d_status, s);
 }
 
+// Lanes a deal launch may have (k_deal_ct's 32-bit lane index) and groups / shares a recover launch may have.
+constexpr uint64_t kDealMaxLanes = 1ull << 31;
+constexpr uint64_t kSplitDeal = 4096;  // deal lanes per context range
+
+bool deal_args_ok(const void* secrets, const void* tails, uint64_t n_val, uint32_t total, uint32_t threshold,
+                  const void* out_shares, const void* status, const void* out_pubs, const void* pub_status) {
+  if (!secrets || !out_shares || !status || threshold == 0 || total == 0 || (threshold > 1 && !tails)) return false;
+  if ((out_pubs == nullptr) != (pub_status == nullptr)) return false;
+  if (mul_overflows(n_val, ((uint64_t)total + 1) * 48) || mul_overflows(n_val, 32 * (uint64_t)threshold)) return false;
+  return n_val * ((uint64_t)total + 1) < kDealMaxLanes;
+}
+
+int hipbls_threshold_split_batch_ct(const uint8_t* secrets, const uint8_t* poly_tails, uint64_t n_val, uint32_t total,
+                                    uint32_t threshold, uint8_t* out_shares, int32_t* status, uint8_t* out_pubs,
+                                    int32_t* pub_status) {
+  if (threshold == 0 || total == 0) return arg_err("bad split arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!deal_args_ok(secrets, poly_tails, n_val, total, threshold, out_shares, status, out_pubs, pub_status))
+    return arg_err("bad split arguments");
+  ENSURE_INIT();
+  const uint64_t per = kSplitDeal / ((uint64_t)total + 1);
+  const uint64_t tail = 32 * (uint64_t)(threshold - 1), row = (uint64_t)total + 1;
+  return run_ranges(plan_ranges(n_val, parts_for(n_val, per ? per : 1), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      return deal_ct_host(c, secrets + 32 * lo, poly_tails ? poly_tails + tail * lo : poly_tails,
+                                          hi - lo, total, threshold, out_shares + 32 * (uint64_t)total * lo, status + lo,
+                                          out_pubs ? out_pubs + 48 * row * lo : out_pubs,
+                                          pub_status ? pub_status + row * lo : pub_status);
+                    });
+}
+
+int hipbls_threshold_split_batch_ct_device(const uint8_t* d_secrets, const uint8_t* d_poly_tails, uint64_t n_val,
+                                           uint32_t total, uint32_t threshold, uint8_t* d_out_shares,
+                                           int32_t* d_status, uint8_t* d_out_pubs, int32_t* d_pub_status,
+                                           void* stream) {
+  if (threshold == 0 || total == 0) return arg_err("bad split arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!deal_args_ok(d_secrets, d_poly_tails, n_val, total, threshold, d_out_shares, d_status, d_out_pubs, d_pub_status))
+    return arg_err("bad split arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_deal_ct(c, d_secrets, d_poly_tails, n_val, total, threshold, d_out_shares, d_status, d_out_pubs,
+                        d_pub_status, s);
+}
+
+int hipbls_recover_secret_batch_ct(const uint8_t* shares, const int64_t* ids, const uint64_t* group_offsets,
+                                   uint64_t n_groups, uint8_t* out_secrets, int32_t* status, uint8_t* out_pubkeys,
+                                   int32_t* pk_status) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!group_offsets || !out_secrets || !status || (out_pubkeys == nullptr) != (pk_status == nullptr) ||
+      n_groups >= kDealMaxLanes)
+    return arg_err("bad recover arguments");
+  if (!groups_ok(group_offsets, n_groups)) return arg_err("bad group offsets");
+  const uint64_t n_parts = group_offsets[n_groups];
+  if ((n_parts && (!shares || !ids)) || n_parts >= kDealMaxLanes) return arg_err("bad recover arguments");
+  ENSURE_INIT();
+  return run_ranges(plan_ranges(n_groups, parts_for(n_groups, kSplitGroups), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      std::vector<uint64_t> tmp;
+                      const uint64_t p0 = group_offsets[lo];
+                      return recover_ct_host(c, shares ? shares + 32 * p0 : shares, ids ? ids + p0 : ids,
+                                             rebase(group_offsets, lo, hi, tmp), hi - lo, out_secrets + 32 * lo,
+                                             status + lo, out_pubkeys ? out_pubkeys + 48 * lo : out_pubkeys,
+                                             pk_status ? pk_status + lo : pk_status);
+                    });
+}
+
+int hipbls_recover_secret_batch_ct_device(const uint8_t* d_shares, const int64_t* d_ids,
+                                          const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
+                                          uint8_t* d_out_secrets, int32_t* d_status, uint8_t* d_out_pubkeys,
+                                          int32_t* d_pk_status, void* stream) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!d_group_offsets || !d_out_secrets || !d_status || (d_out_pubkeys == nullptr) != (d_pk_status == nullptr) ||
+      (n_parts && (!d_shares || !d_ids)) || n_groups >= kDealMaxLanes || n_parts >= kDealMaxLanes)
+    return arg_err("bad recover arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_recover_ct(c, d_shares, d_ids, d_group_offsets, n_groups, n_parts, d_out_secrets, d_status,
+                           d_out_pubkeys, d_pk_status, s);
+}
+
+// One validator / one group of the batched calls above: the same bytes and statuses as ever.
 int hipbls_threshold_split(const uint8_t* secret, const uint8_t* poly_tail, uint32_t total, uint32_t threshold,
                            uint8_t* out_shares, int32_t* status) {
   if (!secret || !out_shares || !status || threshold == 0 || total == 0 || (threshold > 1 && !poly_tail))
     return arg_err("bad split arguments");
-  ENSURE_INIT();
-  Context& c = ctx(0);
-  ENTER_CTX(c);
-  HIP_TRY(c.b_aux.ensure(32 * (uint64_t)threshold));
-  HIP_TRY(c.b_out.ensure(32 * (uint64_t)total));
-  HIP_TRY(c.b_st.ensure(4));
-  HIP_TRY(hipMemcpyAsync(c.b_aux.p, secret, 32, hipMemcpyHostToDevice, c.stream));
-  if (threshold > 1)
-    HIP_TRY(hipMemcpyAsync((uint8_t*)c.b_aux.p + 32, poly_tail, 32 * (uint64_t)(threshold - 1), hipMemcpyHostToDevice,
-                           c.stream));
-  hipLaunchKernelGGL(k_threshold_split, dim3((unsigned)grid_for(total)), dim3(kBlock), 0, c.stream,
-                     (const uint8_t*)c.b_aux.p, (const uint8_t*)c.b_aux.p + 32, total, threshold, (uint8_t*)c.b_out.p,
-                     (int32_t*)c.b_st.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_shares, c.b_out.p, 32 * (uint64_t)total, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, 4, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  return HIPBLS_OK;
+  return hipbls_threshold_split_batch_ct(secret, poly_tail, 1, total, threshold, out_shares, status, nullptr, nullptr);
 }
 
 int hipbls_recover_secret(const uint8_t* shares, const int64_t* ids, uint32_t n, uint8_t* out_secret,
                           int32_t* status) {
   if (!out_secret || !status || (n && (!shares || !ids))) return arg_err("bad recover arguments");
-  ENSURE_INIT();
-  Context& c = ctx(0);
-  ENTER_CTX(c);
-  HIP_TRY(c.b_aux.ensure(32 * (uint64_t)(n ? n : 1)));
-  HIP_TRY(c.b_ids.ensure(8 * (uint64_t)(n ? n : 1)));
-  HIP_TRY(c.b_out.ensure(32));
-  HIP_TRY(c.b_st.ensure(4));
-  if (n) {
-    HIP_TRY(hipMemcpyAsync(c.b_aux.p, shares, 32 * (uint64_t)n, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(hipMemcpyAsync(c.b_ids.p, ids, 8 * (uint64_t)n, hipMemcpyHostToDevice, c.stream));
-  }
-  hipLaunchKernelGGL(k_recover_secret, dim3(1), dim3(kBlock), 0, c.stream, (const uint8_t*)c.b_aux.p,
-                     (const int64_t*)c.b_ids.p, n, (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_secret, c.b_out.p, 32, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, 4, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  return HIPBLS_OK;
+  const uint64_t offs[2] = {0, n};
+  return hipbls_recover_secret_batch_ct(shares, ids, offs, 1, out_secret, status, nullptr, nullptr);
 }
 
 int hipbls_kernel_timing(const char* name, double* avg_ms, uint64_t* launches) {

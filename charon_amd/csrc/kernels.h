@@ -949,66 +949,6 @@ __global__ void __launch_bounds__(kSumBlock) k_g2_sum_final(const uint32_t* __re
   *status = HIPBLS_OK;
 }
 
-// Shamir shares: lane i-1 evaluates share_i = sum_j poly_j i^j (Horner over Fr)
-__global__ void __launch_bounds__(kBlock) k_threshold_split(const uint8_t* __restrict__ secret, const uint8_t* __restrict__ tail,
-                                  uint32_t total, uint32_t threshold, uint8_t* __restrict__ out,
-                                  int32_t* __restrict__ status) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  fr coef, acc, x, r2;
-  for (int w = 0; w < 8; ++w) r2.v[w] = FR_R2[w];
-  fr_from_u32(x, i + 1);
-  bool ok = true;
-  for (int w = 0; w < 8; ++w) acc.v[w] = 0;
-  for (int j = (int)threshold - 1; j >= 0; --j) {
-    const uint8_t* c = j == 0 ? secret : tail + 32 * (j - 1);
-    if (!fr_plain_from_be32(coef, c)) ok = false;
-    fr_mul(coef, coef, r2);  // to Montgomery
-    fr_mul(acc, acc, x);
-    fr_add(acc, acc, coef);
-  }
-  fr plain;
-  fr_to_plain(plain, acc);
-  for (int w = 0; w < 8; ++w)
-    for (int b = 0; b < 4; ++b) out[32 * i + 31 - 4 * w - b] = ok ? (uint8_t)(plain.v[w] >> (8 * b)) : (uint8_t)0;
-  if (i == 0) *status = ok ? HIPBLS_OK : HIPBLS_ERR_SECRET;
-}
-
-__global__ void __launch_bounds__(kBlock) k_recover_secret(const uint8_t* __restrict__ shares, const int64_t* __restrict__ ids, uint32_t n,
-                                 uint8_t* __restrict__ out, int32_t* __restrict__ status) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  int st = n > 0 ? HIPBLS_OK : HIPBLS_ERR_COMBINE;
-  for (uint32_t a = 0; a < n; ++a) {
-    if (ids[a] == 0) st = HIPBLS_ERR_COMBINE;
-    for (uint32_t b = a + 1; b < n; ++b)
-      if (ids[a] == ids[b]) st = HIPBLS_ERR_COMBINE;
-  }
-  fr acc, r2;
-  for (int w = 0; w < 8; ++w) {
-    acc.v[w] = 0;
-    r2.v[w] = FR_R2[w];
-  }
-  for (uint32_t k = 0; k < n && st == HIPBLS_OK; ++k) {
-    fr s, lam;
-    if (!fr_plain_from_be32(s, shares + 32 * k)) {
-      st = HIPBLS_ERR_SECRET;
-      break;
-    }
-    lagrange_at_zero(lam, ids, (int)n, (int)k);  // plain
-    fr_mul(lam, lam, r2);
-    fr_mul(s, s, r2);
-    fr_mul(s, s, lam);
-    fr_add(acc, acc, s);
-  }
-  fr plain;
-  fr_to_plain(plain, acc);
-  for (int w = 0; w < 8; ++w)
-    for (int b = 0; b < 4; ++b)
-      out[31 - 4 * w - b] = st == HIPBLS_OK ? (uint8_t)(plain.v[w] >> (8 * b)) : (uint8_t)0;
-  *status = st;
-}
-
-
 // ---------------------------------------------------------------- RLC BatchVerify (rlc.h)
 // The four stages run per sub-batch (a contiguous, window-aligned item range) so that several
 // sub-batches' stages overlap on separate streams (launch_rlc).

@@ -117,6 +117,12 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_secret_to_public_key_batch_ct": ([u8p, u64, u8p, i32p], ctypes.c_int),
         "hipbls_sign_batch_ct_device": ([vp, vp, vp, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_secret_to_public_key_batch_ct_device": ([vp, u64, vp, vp, vp], ctypes.c_int),
+        "hipbls_threshold_split_batch_ct": ([u8p, u8p, u64, ctypes.c_uint32, ctypes.c_uint32, u8p, i32p, u8p, i32p],
+                                            ctypes.c_int),
+        "hipbls_recover_secret_batch_ct": ([u8p, i64p, u64p, u64, u8p, i32p, u8p, i32p], ctypes.c_int),
+        "hipbls_threshold_split_batch_ct_device": ([vp, vp, u64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp],
+                                                   ctypes.c_int),
+        "hipbls_recover_secret_batch_ct_device": ([vp, vp, vp, u64, u64, vp, vp, vp, vp, vp], ctypes.c_int),
         "hipbls_batch_verify_rlc": ([u8p, u8p, u32p, u64, u8p, u64p, u64, u8p, i32p], ctypes.c_int),
         "hipbls_batch_verify_rlc_device": ([vp, vp, vp, u64, vp, vp, u64, u8p, vp, vp], ctypes.c_int),
         "hipbls_rlc_stats": ([u64p, u64p, u64p], ctypes.c_int),
@@ -173,6 +179,8 @@ def exported_symbols() -> List[str]:
         "hipbls_rootcache_config", "hipbls_rootcache_stats",
         "hipbls_sign_batch_ct", "hipbls_secret_to_public_key_batch_ct", "hipbls_sign_batch_ct_device",
         "hipbls_secret_to_public_key_batch_ct_device",
+        "hipbls_threshold_split_batch_ct", "hipbls_recover_secret_batch_ct",
+        "hipbls_threshold_split_batch_ct_device", "hipbls_recover_secret_batch_ct_device",
     ]
 
 
@@ -296,16 +304,76 @@ class HipBLS:
         raw = out.raw
         return [raw[48 * i:48 * i + 48] for i in range(n)], list(st)[:n]
 
+    def threshold_split_batch_ct(self, secrets_: Sequence[bytes], tails: Sequence[Sequence[bytes]], total: int,
+                                 threshold: int, with_pubs: bool = True):
+        """Deal many validators in one call on the secret-independent kernels (hipbls_threshold_split_batch_ct):
+        validator v's polynomial is secrets_[v] + tails[v][0] x + ... (threshold - 1 tail coefficients each).
+        Returns (shares, status, pubs, pub_status): shares[v] = {i: f_v(i)} for i = 1..total, status[v] OK or
+        ERR_SECRET (its outputs are then zero bytes); with with_pubs, pubs[v][k] is [f_v(k)] g1 compressed, k = 0
+        the root key and k = 1..total the pubshares, with pub_status[v][k] as secret_to_public_key_batch_ct gives
+        it; without, both are None."""
+        n = len(secrets_)
+        if len(tails) != n:
+            raise ValueError("one polynomial tail per secret")
+        _check_lengths("secret keys", secrets_, 32)
+        for t in tails:
+            if len(t) != max(threshold, 1) - 1:
+                raise ValueError("a polynomial tail has threshold - 1 coefficients")
+            _check_lengths("polynomial coefficients", t, 32)
+        row = total + 1
+        out = ctypes.create_string_buffer(32 * max(n * total, 1))
+        st = _status_array(n)
+        pubs = ctypes.create_string_buffer(48 * max(n * row, 1)) if with_pubs else None
+        pst = _status_array(n * row) if with_pubs else None
+        _check(self.lib.hipbls_threshold_split_batch_ct(b"".join(secrets_), b"".join(b"".join(t) for t in tails), n,
+                                                        total, threshold, out, st, pubs, pst), self.lib)
+        raw = out.raw
+        shares = [{i + 1: raw[32 * (total * v + i):32 * (total * v + i) + 32] for i in range(total)} for v in range(n)]
+        if not with_pubs:
+            return shares, list(st)[:n], None, None
+        praw, plist = pubs.raw, list(pst)
+        return (shares, list(st)[:n],
+                [[praw[48 * (row * v + k):48 * (row * v + k) + 48] for k in range(row)] for v in range(n)],
+                [plist[row * v:row * v + row] for v in range(n)])
+
+    def recover_secret_batch_ct(self, groups: Sequence[Mapping[int, bytes]], with_pubkeys: bool = True):
+        """Recover many secrets in one call on the secret-independent kernels (hipbls_recover_secret_batch_ct): group
+        g is a {share id: share} map.  Returns (secrets, status, pubkeys, pk_status): status[g] OK, ERR_COMBINE (empty
+        group, id 0, duplicate id) or ERR_SECRET (a share >= r), the secret zero bytes unless OK; with with_pubkeys
+        the recovered secret's public key and its status, else None for both."""
+        n = len(groups)
+        ids, shares, offs = [], [], (ctypes.c_uint64 * (n + 1))()
+        for g, grp in enumerate(groups):
+            offs[g] = len(ids)
+            for i, sh in grp.items():
+                ids.append(_go_int(i))
+                shares.append(sh)
+        offs[n] = len(ids)
+        _check_lengths("shares", shares, 32)
+        arr = (ctypes.c_int64 * max(len(ids), 1))(*ids)
+        out = ctypes.create_string_buffer(32 * max(n, 1))
+        st = _status_array(n)
+        pks = ctypes.create_string_buffer(48 * max(n, 1)) if with_pubkeys else None
+        pst = _status_array(n) if with_pubkeys else None
+        _check(self.lib.hipbls_recover_secret_batch_ct(b"".join(shares), arr, offs, n, out, st, pks, pst), self.lib)
+        raw = out.raw
+        secs = [raw[32 * g:32 * g + 32] for g in range(n)]
+        if not with_pubkeys:
+            return secs, list(st)[:n], None, None
+        praw = pks.raw
+        return secs, list(st)[:n], [praw[48 * g:48 * g + 48] for g in range(n)], list(pst)[:n]
+
     def _split(self, secret: bytes, total: int, threshold: int, tail: Sequence[bytes]) -> Dict[int, bytes]:
+        """One validator of threshold_split_batch_ct.  Exceptions and texts are those of the former single call; in
+        addition a tail that has not threshold - 1 coefficients, or a secret or coefficient that is not 32 bytes, is
+        now a ValueError (threshold_split_batch_ct's checks) where the bytes used to be handed to the library as they
+        were.  threshold_split and threshold_split_insecure always build a well-formed tail."""
         if int.from_bytes(secret, "big") >= R:
             raise TBLSError("cannot unmarshal bytes into Herumi secret key")
-        out = ctypes.create_string_buffer(32 * total)
-        st = _status_array(1)
-        _check(self.lib.hipbls_threshold_split(secret, b"".join(tail), total, threshold, out, st), self.lib)
+        shares, st, _, _ = self.threshold_split_batch_ct([secret], [list(tail)], total, threshold, with_pubs=False)
         if st[0] != OK:
             raise TBLSError("cannot unmarshal bytes into Herumi secret key")
-        raw = out.raw
-        return {i + 1: raw[32 * i:32 * i + 32] for i in range(total)}
+        return shares[0]
 
     def threshold_split(self, secret: bytes, total: int, threshold: int) -> Dict[int, bytes]:
         """herumi.go:134-181: polynomial tail from the CSPRNG."""
@@ -324,13 +392,10 @@ class HipBLS:
         for i in ids:
             if int.from_bytes(shares[i], "big") >= R:
                 raise TBLSError("cannot unmarshal key with into Herumi secret key")
-        arr = (ctypes.c_int64 * max(len(ids), 1))(*[_go_int(i) for i in ids])
-        out = ctypes.create_string_buffer(32)
-        st = _status_array(1)
-        _check(self.lib.hipbls_recover_secret(b"".join(shares[i] for i in ids), arr, len(ids), out, st), self.lib)
+        secs, st, _, _ = self.recover_secret_batch_ct([{i: shares[i] for i in ids}], with_pubkeys=False)
         if st[0] != OK:
             raise TBLSError("cannot recover full private key from partial keys")
-        return out.raw
+        return secs[0]
 
     # ---------------------------------------------------------------- hot path
     def sign(self, private_key: bytes, data: bytes) -> bytes:

@@ -25,6 +25,9 @@
  *   hipbls_aggregate                   tbls.Implementation.Aggregate         tbls/tbls.go:65-67, tbls/herumi.go:220-242
  *   hipbls_threshold_split             tbls.Implementation.ThresholdSplit[Insecure] tbls/tbls.go:40-47, tbls/herumi.go:84-181
  *   hipbls_recover_secret              tbls.Implementation.RecoverSecret     tbls/tbls.go:49, tbls/herumi.go:183-218
+ *   hipbls_threshold_split_batch_ct, hipbls_recover_secret_batch_ct: the same two for many validators in one call, with
+ *                                      the public keys their callers ask for next (dkg/keycast.go:156-179,
+ *                                      cmd/combine/combine.go:106-119); the two single calls are one-validator calls of them
  *   hipbls_pubshare_table_load         the pubshare set charon builds from the cluster lock at startup
  *                                      (app/app.go:343-381, core/parsigex/parsigex.go:139-163 lookup)
  *   hipbls_verify_batch_keys           tbls.Verify with that pubshare (tbls/herumi.go:285-301)
@@ -248,14 +251,47 @@ int hipbls_aggregate(const uint8_t* sigs, uint64_t n, uint8_t* out_sig, int32_t*
 
 /* Shamir split: share_i = secret + sum_j poly_tail[j] * i^(j+1) mod r, i = 1..total.
  * poly_tail holds threshold-1 secrets of 32 bytes (the reference draws them from a CSPRNG or an
- * insecure reader; the caller supplies them).  *status = OK | ERR_SECRET. */
+ * insecure reader; the caller supplies them).  *status = OK | ERR_SECRET.  A one-validator call of
+ * hipbls_threshold_split_batch_ct without public keys. */
 int hipbls_threshold_split(const uint8_t* secret, const uint8_t* poly_tail, uint32_t total, uint32_t threshold,
                            uint8_t* out_shares, int32_t* status);
 
 /* Lagrange recovery of the secret at 0 from n (id, share) pairs; ids as in ThresholdAggregate (int mod r).
- * *status = OK | ERR_SECRET | ERR_COMBINE. */
+ * *status = OK | ERR_SECRET | ERR_COMBINE.  A one-group call of hipbls_recover_secret_batch_ct. */
 int hipbls_recover_secret(const uint8_t* shares, const int64_t* ids, uint32_t n, uint8_t* out_secret,
                           int32_t* status);
+
+/* Deal n_val validators in one call, on kernels whose instruction stream and memory addresses do not depend on the
+ * secrets.  Validator v has secret secrets[32 v ..] and polynomial tail
+ * poly_tails[32 (threshold-1) v ..] (threshold-1 coefficients).
+ * out_shares[32 (total v + i-1) ..] = f_v(i), i = 1..total: exactly hipbls_threshold_split's bytes.
+ * status[v] = OK | ERR_SECRET (the secret or any coefficient >= r: every output of that validator is zero bytes).
+ * out_pubs / pub_status (both null, or both given): entry v (total+1) + k is [f_v(k)] g1 compressed, k = 0 the
+ * root key, k = 1..total the pubshares, with exactly hipbls_secret_to_public_key_batch_ct's bytes and status for
+ * that scalar (ERR_SECRET and zero bytes for a zero scalar, and for every entry of a validator whose status[v]
+ * is ERR_SECRET).  One kernel (timed as deal_ct), one lane per (v, k): Horner over the public threshold, then
+ * [f_v(k)] g1 by 64 mixed additions over a fixed-base comb of g1 that each context builds once, at first use (timed as
+ * g1_comb_build, on the library's stream; calls are ordered behind it by a stream wait, never a host wait).
+ * n_val == 0 is OK; threshold == 0, total == 0, a null tail with
+ * threshold > 1, only one of out_pubs / pub_status, or n_val (total+1) >= 2^31 is HIPBLS_ERR_ARG.  Validators are
+ * split over the contexts whole.  The device copies of secrets, tails and shares are zeroed on the call's stream before
+ * the call returns. */
+int hipbls_threshold_split_batch_ct(const uint8_t* secrets, const uint8_t* poly_tails, uint64_t n_val,
+                                    uint32_t total, uint32_t threshold, uint8_t* out_shares, int32_t* status,
+                                    uint8_t* out_pubs, int32_t* pub_status);
+
+/* Recover n_groups secrets in one call, secret-independent as above (kernel timed as recover_ct, one lane per group).
+ * Group g: shares[32 k ..], ids[k] for k in [group_offsets[g], group_offsets[g+1]); ids as hipbls_recover_secret.
+ * status[g] = OK | ERR_COMBINE (empty, id 0, duplicate id: public, decided first) | ERR_SECRET (a share >= r).
+ * out_secrets[32 g ..] as hipbls_recover_secret (zero bytes on error).
+ * out_pubkeys / pk_status (both null or both given): [secret_g] g1 as above (ERR_SECRET and zero bytes for a group
+ * that failed or a zero secret).  The ids and the group sizes are public: the Lagrange coefficients are computed from
+ * them by variable-time code, and every lane runs as many steps as the call's largest group has shares.  n_groups == 0
+ * is OK; n_groups or the share count >= 2^31 is HIPBLS_ERR_ARG.  Groups are split over the contexts whole; the device
+ * copies of the shares and of the recovered secrets are zeroed before the call returns. */
+int hipbls_recover_secret_batch_ct(const uint8_t* shares, const int64_t* ids, const uint64_t* group_offsets,
+                                   uint64_t n_groups, uint8_t* out_secrets, int32_t* status,
+                                   uint8_t* out_pubkeys, int32_t* pk_status);
 
 /* Random-linear-combination BatchVerify.  Item i is (pks[48 i..], message msg_idx[i], sigs[96 i..]);
  * message m is msgs[msg_offsets[m] .. msg_offsets[m+1]) (n_msgs distinct messages, each hashed once).
@@ -424,6 +460,18 @@ int hipbls_sign_batch_ct_device(const uint8_t* d_sks, const uint8_t* d_msgs, con
                                 uint64_t n, uint8_t* d_out_sigs, int32_t* d_status, void* stream);
 int hipbls_secret_to_public_key_batch_ct_device(const uint8_t* d_sks, uint64_t n, uint8_t* d_out_pks,
                                                 int32_t* d_status, void* stream);
+
+/* Device variants of hipbls_threshold_split_batch_ct / hipbls_recover_secret_batch_ct: they only enqueue (the first
+ * call on a context also enqueues the build of its comb table, and the call's stream waits for it on the device).
+ * n_parts = group_offsets[n_groups], passed explicitly.  The secrets stay in the caller's buffers; clearing them is the caller's. */
+int hipbls_threshold_split_batch_ct_device(const uint8_t* d_secrets, const uint8_t* d_poly_tails, uint64_t n_val,
+                                           uint32_t total, uint32_t threshold, uint8_t* d_out_shares,
+                                           int32_t* d_status, uint8_t* d_out_pubs, int32_t* d_pub_status,
+                                           void* stream);
+int hipbls_recover_secret_batch_ct_device(const uint8_t* d_shares, const int64_t* d_ids,
+                                          const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
+                                          uint8_t* d_out_secrets, int32_t* d_status, uint8_t* d_out_pubkeys,
+                                          int32_t* d_pk_status, void* stream);
 
 /* As hipbls_batch_verify_rlc; seed32 is a host pointer.  An out-of-range msg_idx[i] yields
  * status[i] = HIPBLS_ERR_ARG. */

@@ -292,3 +292,117 @@ func distinctRoots(msgs [][]byte) ([][]byte, []uint32) {
 
 	return roots, midx
 }
+
+// Dealt is one validator's result of BatchThresholdSplit: the shares f(i) and their public keys, i = 1..total, and the
+// root public key [f(0)] g1.
+type Dealt struct {
+	Shares    map[int]tbls.PrivateKey
+	PubKey    tbls.PublicKey
+	PubShares map[int]tbls.PublicKey
+}
+
+// BatchThresholdSplit deals every secret in one call: what dkg/keycast.go:156-179 does per validator
+// (SecretToPublicKey of the root, ThresholdSplit, SecretToPublicKey of each share), on kernels whose instruction stream
+// and memory addresses do not depend on the secrets (hipbls_threshold_split_batch_ct).  The polynomial tails come from
+// crypto/rand as ThresholdSplit's do.  errs[v] is what the serial calls return for validator v.
+func (h HipBLS) BatchThresholdSplit(secrets []tbls.PrivateKey, total, threshold uint) ([]Dealt, []error, error) {
+	n := len(secrets)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	flat := make([]byte, 0, 32*n)
+	poly := make([]byte, 0, 32*n*int(threshold))
+	for _, s := range secrets {
+		flat = append(flat, s[:]...)
+		for i := 1; i < int(threshold); i++ {
+			k, err := h.GenerateSecretKey()
+			if err != nil {
+				return nil, nil, err
+			}
+			poly = append(poly, k[:]...)
+		}
+	}
+	row := int(total) + 1
+	shares := make([]byte, 32*n*int(total))
+	pubs := make([]byte, 48*n*row)
+	status := make([]int32, n)
+	pubStatus := make([]int32, n*row)
+	if rc := C.hipbls_threshold_split_batch_ct(u8(flat), u8(poly), C.uint64_t(n), C.uint32_t(total),
+		C.uint32_t(threshold), u8(shares), i32(status), u8(pubs), i32(pubStatus)); rc != C.HIPBLS_OK {
+		return nil, nil, observeFailure("threshold_split", n, devErr(rc))
+	}
+	out := make([]Dealt, n)
+	errs := make([]error, n)
+	for v := range secrets {
+		if status[v] != C.HIPBLS_OK {
+			errs[v] = errors.New("cannot unmarshal bytes into Herumi secret key")
+			continue
+		}
+		d := Dealt{Shares: make(map[int]tbls.PrivateKey, total), PubShares: make(map[int]tbls.PublicKey, total)}
+		for k := 0; k < row; k++ {
+			if pubStatus[v*row+k] != C.HIPBLS_OK { // a zero scalar: GetSafePublicKey fails (herumi.go:74)
+				errs[v] = errors.New("cannot obtain public key from secret")
+				break
+			}
+			var pk tbls.PublicKey
+			copy(pk[:], pubs[48*(v*row+k):])
+			if k == 0 {
+				d.PubKey = pk
+				continue
+			}
+			var sk tbls.PrivateKey
+			copy(sk[:], shares[32*(v*int(total)+k-1):])
+			d.Shares[k] = sk
+			d.PubShares[k] = pk
+		}
+		if errs[v] == nil {
+			out[v] = d
+		}
+	}
+	observe("threshold_split", errs)
+
+	return out, errs, nil
+}
+
+// BatchRecoverSecret recovers one secret per group and its public key in one call: what cmd/combine/combine.go:106-119
+// does per validator (RecoverSecret, SecretToPublicKey), secret-independent (hipbls_recover_secret_batch_ct).  errs[g]
+// is what the serial calls return for group g.
+func (HipBLS) BatchRecoverSecret(groups []map[int]tbls.PrivateKey) ([]tbls.PrivateKey, []tbls.PublicKey, []error, error) {
+	n := len(groups)
+	if n == 0 {
+		return nil, nil, nil, nil
+	}
+	var flat []byte
+	var ids []int64
+	offs := []uint64{0}
+	for _, g := range groups {
+		for idx, k := range g {
+			flat = append(flat, k[:]...)
+			ids = append(ids, int64(idx))
+		}
+		offs = append(offs, uint64(len(ids)))
+	}
+	secrets := make([]tbls.PrivateKey, n)
+	pks := make([]tbls.PublicKey, n)
+	status := make([]int32, n)
+	pkStatus := make([]int32, n)
+	if rc := C.hipbls_recover_secret_batch_ct(u8(flat), i64(ids), u64(offs), C.uint64_t(n),
+		(*C.uint8_t)(unsafe.Pointer(&secrets[0][0])), i32(status), (*C.uint8_t)(unsafe.Pointer(&pks[0][0])),
+		i32(pkStatus)); rc != C.HIPBLS_OK {
+		return nil, nil, nil, observeFailure("recover_secret", n, devErr(rc))
+	}
+	errs := make([]error, n)
+	for g := range groups {
+		switch {
+		case status[g] == C.HIPBLS_ERR_SECRET:
+			errs[g] = errors.New("cannot unmarshal key with into Herumi secret key")
+		case status[g] != C.HIPBLS_OK:
+			errs[g] = errors.New("cannot recover full private key from partial keys")
+		case pkStatus[g] != C.HIPBLS_OK:
+			errs[g] = errors.New("cannot obtain public key from secret")
+		}
+	}
+	observe("recover_secret", errs)
+
+	return secrets, pks, errs, nil
+}

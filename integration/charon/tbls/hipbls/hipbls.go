@@ -347,6 +347,7 @@ func (HipBLS) SecretToPublicKey(secret tbls.PrivateKey) (tbls.PublicKey, error) 
 	return pk, nil
 }
 
+// split runs on the secret-independent kernels (hipbls_threshold_split_batch_ct, DESIGN.md 4.13).
 func (h HipBLS) split(secret tbls.PrivateKey, total, threshold uint, tail func() (tbls.PrivateKey, error)) (map[int]tbls.PrivateKey, error) {
 	if !validScalar(secret) {
 		return nil, errors.New("cannot unmarshal bytes into Herumi secret key")
@@ -361,8 +362,9 @@ func (h HipBLS) split(secret tbls.PrivateKey, total, threshold uint, tail func()
 	}
 	out := make([]byte, 32*int(total))
 	status := make([]int32, 1)
-	if rc := C.hipbls_threshold_split(u8(secret[:]), u8(poly), C.uint32_t(total), C.uint32_t(threshold), u8(out),
-		i32(status)); rc != C.HIPBLS_OK {
+	// one validator of the batched, secret-independent call (no public keys asked for)
+	if rc := C.hipbls_threshold_split_batch_ct(u8(secret[:]), u8(poly), 1, C.uint32_t(total), C.uint32_t(threshold),
+		u8(out), i32(status), nil, nil); rc != C.HIPBLS_OK {
 		return nil, devErr(rc)
 	}
 	if status[0] != C.HIPBLS_OK {
@@ -404,7 +406,10 @@ func (HipBLS) RecoverSecret(shares map[int]tbls.PrivateKey, _, _ uint) (tbls.Pri
 	}
 	var out tbls.PrivateKey
 	status := make([]int32, 1)
-	if rc := C.hipbls_recover_secret(u8(flat), i64(ids), C.uint32_t(len(ids)), u8(out[:]), i32(status)); rc != C.HIPBLS_OK {
+	// one group of the batched, secret-independent call (no public key asked for)
+	offs := []uint64{0, uint64(len(ids))}
+	if rc := C.hipbls_recover_secret_batch_ct(u8(flat), i64(ids), u64(offs), 1, u8(out[:]), i32(status), nil,
+		nil); rc != C.HIPBLS_OK {
 		return tbls.PrivateKey{}, devErr(rc)
 	}
 	if status[0] != C.HIPBLS_OK {
