@@ -223,6 +223,14 @@ struct RootCache {
   uint64_t gen_base = 0;   // the insert counter when this generation began
   uint64_t rollovers = 0;  // generations ended since the last config
   bool partition = true;   // hits to the front (HIPBLS_ROOTCACHE_PARTITION=0: identity order)
+  // The line pool (rootcache.h line blocks): allocated by the first fused launch that could use it
+  // (rootcache_lines_ensure), never zeroed; its counters are.
+  uint64_t lines_want = kLinesDefault;  // blocks asked for; kLinesDefault: slots / 2, what ends a generation
+  uint64_t line_blocks = 0;             // blocks allocated
+  uint32_t* lines = nullptr;
+  unsigned long long* lctr = nullptr;  // bls::RL_CTRS counters (all since the last config, but the bump counter)
+  static constexpr uint64_t kLinesDefault = ~0ull;
+  uint64_t lines_target() const { return !slots ? 0 : (lines_want == kLinesDefault ? slots / 2 : lines_want); }
   bls::rootcache dev() const {
     bls::rootcache r{};
     if (slots) {
@@ -230,12 +238,18 @@ struct RootCache {
       r.claim = claim;
       r.ctr = ctr;
       r.mask = (uint32_t)(slots - 1);
+      if (lines && lctr) {
+        r.lines = lines;
+        r.lctr = lctr;
+        r.blocks = (uint32_t)line_blocks;
+      }
     }
     return r;
   }
 };
 constexpr uint64_t kRootCacheDefaultSlots = 262144;  // x 256 B = 64 MiB (+ 1 MiB of claims) per context
 constexpr uint64_t kRootCacheMaxSlots = 1ull << 22;
+constexpr uint64_t kRootCacheMaxLines = 1ull << 22;  // x 19,712 B; the default is half the slots (2.4 GiB at 262,144)
 
 // One open or running batch of the submission queue.
 struct VBatch {
@@ -486,6 +500,13 @@ int rootcache_setup(RootCache& rc, uint64_t slots, hipStream_t s) {
   if (!rc.ctr) HIP_TRY(hipMalloc((void**)&rc.ctr, 3 * sizeof(unsigned long long)));
   if (!rc.h_ins) HIP_TRY(hipHostMalloc((void**)&rc.h_ins, sizeof(unsigned long long), hipHostMallocDefault));
   HIP_TRY(hipMemsetAsync(rc.ctr, 0, 3 * sizeof(unsigned long long), s));
+  // the emptied table names no line block, so the pool starts over; one of another size is re-created on demand
+  if (rc.lines && rc.line_blocks != rc.lines_target()) {
+    (void)hipFree(rc.lines);
+    rc.lines = nullptr;
+    rc.line_blocks = 0;
+  }
+  if (rc.lctr) HIP_TRY(hipMemsetAsync(rc.lctr, 0, bls::RL_CTRS * sizeof(unsigned long long), s));
   if (rc.slots) {
     HIP_TRY(hipMemsetAsync(rc.claim, 0, rc.slots * 4, s));
     HIP_TRY(hipMemsetAsync(rc.entries, 0, rc.slots * bls::RC_WORDS * 4, s));
@@ -507,6 +528,49 @@ uint64_t rootcache_default_slots() {
     return kRootCacheDefaultSlots;
   }
   return (uint64_t)v;
+}
+
+// HIPBLS_ROOTCACHE_LINES sets the line pool's block count; 0 turns the lines off.
+uint64_t rootcache_default_lines() {
+  const char* e = getenv("HIPBLS_ROOTCACHE_LINES");
+  if (!e || !e[0]) return RootCache::kLinesDefault;
+  char* end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  if (end == e || *end || v > kRootCacheMaxLines) {
+    fprintf(stderr, "hipbls: HIPBLS_ROOTCACHE_LINES=%s ignored (expected 0 .. 2^22)\n", e);
+    return RootCache::kLinesDefault;
+  }
+  return (uint64_t)v;
+}
+
+// The line pool, allocated by the first fused launch that could use it, so a process that never takes the fused route
+// pays nothing.  RootCache::mu is held and the context's device is current.  A pool that cannot be had leaves the
+// lines off (the fused kernel then runs its full loop, as without them) and says so once.
+void rootcache_lines_ensure(RootCache& rc, hipStream_t s) {
+  const uint64_t want = rc.lines_target();
+  if (!want || rc.lines) return;
+  if (!rc.lctr) {
+    if (hipMalloc((void**)&rc.lctr, bls::RL_CTRS * sizeof(unsigned long long)) != hipSuccess) {
+      (void)hipGetLastError();
+      rc.lctr = nullptr;
+      rc.lines_want = 0;
+      return;
+    }
+    if (hipMemsetAsync(rc.lctr, 0, bls::RL_CTRS * sizeof(unsigned long long), s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError();
+      rc.lines_want = 0;
+      return;
+    }
+  }
+  if (hipMalloc((void**)&rc.lines, want * bls::RL_BLOCK_WORDS * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    fprintf(stderr, "hipbls: no memory for %llu line blocks of the root cache; lines off\n", (unsigned long long)want);
+    rc.lines = nullptr;
+    rc.lines_want = 0;
+    return;
+  }
+  rc.line_blocks = want;
 }
 
 // Held across "copy the cache struct, enqueue the kernel" (KeyCache::mu).
@@ -574,7 +638,7 @@ const KernelRef kKernels[] = {
     KREF(k_scan_apply), KREF(k_scan_part), KREF(k_scan_top), KREF(k_sign), KREF(k_signing_roots), KREF(k_sk_to_pk),
     KREF(k_tagg_scale), KREF(k_tagg_sum), KREF(k_tagg_sum_s), KREF(k_tagg_unscale),
     KREF(k_tv_check_unscale), KREF(k_tv_join), KREF(k_tv_phase_a), KREF(k_tv_prep_pk), KREF(k_tv_prep_pk2),
-    KREF(k_verify_fused), KREF(k_verify_keys), KREF(k_verify_pair_lg2), KREF(k_verify_pair_lq4),
+    KREF(k_verify_fused), KREF(k_verify_fused_lines), KREF(k_verify_keys), KREF(k_verify_pair_lg2), KREF(k_verify_pair_lq4),
     KREF(k_verify_pair_single), KREF(k_verify_prep), KREF(k_zero_sig_status), KREF8(k_g1m_miller8),
     KREF8(k_rlcb_final8), KREF8(k_rlcb_sfactor8), KREF8(k_verify_pair_lq8), KREF8(k_verify_prep8),
     KREF16(k_verify_pair_lq16), KREF8(k_fav_prep8), KREF16W(k_fav_pair_lq16),
@@ -746,6 +810,7 @@ int init_locked(const std::vector<int>& ids) {
       if (krc) return krc;
       const char* part = getenv("HIPBLS_ROOTCACHE_PARTITION");
       c->rcache.partition = !(part && part[0] == '0');
+      c->rcache.lines_want = rootcache_default_lines();
       const int rrc = rootcache_setup(c->rcache, rootcache_default_slots(), c->stream);
       if (rrc) return rrc;
     }
@@ -1221,6 +1286,9 @@ int rootcache_roll_if_due(Context& c, bool ctx_locked) {
   HIP_TRY(hipMemcpyAsync(&ins, R.ctr + 2, sizeof(ins), hipMemcpyDeviceToHost, c.stream));
   HIP_TRY(hipMemsetAsync(R.claim, 0, R.slots * 4, c.stream));
   HIP_TRY(hipMemsetAsync(R.entries, 0, R.slots * bls::RC_WORDS * 4, c.stream));
+  // the line pool is handed out from its start again; it is not zeroed (rootcache.h: a block checks itself under its
+  // root's seed)
+  if (R.lctr) HIP_TRY(hipMemsetAsync(R.lctr + bls::RL_CTR_NEXT, 0, sizeof(unsigned long long), c.stream));
   HIP_TRY(hipStreamSynchronize(c.stream));
   *R.h_ins = ins;
   R.gen_base = ins;
@@ -1237,6 +1305,7 @@ int launch_verify_fused(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs,
   int rc = rootcache_roll_if_due(c, ctx_locked);
   if (rc) return rc;
   std::lock_guard<std::mutex> rg(R.mu);
+  if (n <= 0xffffffffull) rootcache_lines_ensure(R, s);
   const bls::rootcache rcd = n <= 0xffffffffull ? R.dev() : bls::rootcache{};  // perm holds 32-bit indices
   uint32_t *perm = nullptr, *pslot = nullptr;
   if (rcd.entries) {
@@ -1254,8 +1323,10 @@ int launch_verify_fused(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs,
   }
   rc = timed(c, "verify", s, [&] {
     KC_LAUNCH_GUARD(c);
-    hipLaunchKernelGGL(k_verify_fused, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_pks, d_msgs, d_offs, d_sigs,
-                       n, d_status, c.kcache.dev(), rcd, (const uint32_t*)perm, (const uint32_t*)pslot);
+    // with a line pool the kernel that replays and fills blocks; without one the kernel as it was before the lines
+    hipLaunchKernelGGL(rcd.lines ? k_verify_fused_lines : k_verify_fused, dim3((unsigned)grid_for(n)), dim3(kBlock), 0,
+                       s, d_pks, d_msgs, d_offs, d_sigs, n, d_status, c.kcache.dev(), rcd, (const uint32_t*)perm,
+                       (const uint32_t*)pslot);
   });
   if (rc) return rc;
   // the insert counter, for the next call's generation check: a copy behind the kernel, never waited for
@@ -4351,6 +4422,43 @@ int hipbls_rootcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, 
     *misses += v[1];
     *inserts += v[2];
     *rollovers += c.rcache.rollovers;
+  }
+  return HIPBLS_OK;
+}
+
+// The line pool's size (blocks; 0: off; UINT64_MAX: the default, half the slots).  As hipbls_rootcache_config, which it ends with: the table is emptied, since
+// its entries name blocks of the pool that goes, and every counter starts over.
+int hipbls_rootcache_lines_config(uint64_t blocks) {
+  if (blocks != RootCache::kLinesDefault && blocks > kRootCacheMaxLines)
+    return arg_err("root cache line pool above 2^22 blocks");
+  ENSURE_INIT();
+  return run_all([&](Context& c) -> int {
+    std::lock_guard<std::mutex> g(c.rcache.mu);
+    HIP_TRY(hipDeviceSynchronize());
+    c.rcache.lines_want = blocks;
+    return rootcache_setup(c.rcache, c.rcache.slots, c.stream);
+  });
+}
+
+int hipbls_rootcache_lines_stats(uint64_t* line_hits, uint64_t* blocks_published, uint64_t* pool_full,
+                                 uint64_t* check_failures) {
+  if (!line_hits || !blocks_published || !pool_full || !check_failures) return arg_err("null output");
+  *line_hits = *blocks_published = *pool_full = *check_failures = 0;
+  ENSURE_INIT();
+  const int n = nctx();
+  for (int k = 0; k < n; ++k) {
+    Context& c = ctx(k);
+    ENTER_CTX(c);
+    std::lock_guard<std::mutex> g(c.rcache.mu);
+    if (!c.rcache.lctr) continue;
+    unsigned long long v[bls::RL_CTRS] = {};
+    HIP_TRY(hipDeviceSynchronize());  // the counters of every call that has been enqueued
+    HIP_TRY(hipMemcpyAsync(v, c.rcache.lctr, sizeof(v), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    *line_hits += v[bls::RL_CTR_HITS];
+    *blocks_published += v[bls::RL_CTR_PUBLISHED];
+    *pool_full += v[bls::RL_CTR_FULL];
+    *check_failures += v[bls::RL_CTR_BAD];
   }
   return HIPBLS_OK;
 }

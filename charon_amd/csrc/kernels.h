@@ -24,13 +24,14 @@ constexpr int kBlock = 64;
   __shared__ u32x4 s_f12_[36 * kBlock];      \
   const f12l<kBlock> F { (BLS_LDS u32x4*)&s_f12_[threadIdx.x] }  // one wave per workgroup: these kernels are register-bound, not LDS-bound
 
-__global__ void __launch_bounds__(kBlock) k_verify_fused(const uint8_t* __restrict__ pks,
-                                                         const uint8_t* __restrict__ msgs,
-                                                         const uint64_t* __restrict__ offs,
-                                                         const uint8_t* __restrict__ sigs, uint64_t n,
-                                                         int32_t* __restrict__ status, keycache kc, rootcache rc,
-                                                         const uint32_t* __restrict__ perm,
-                                                         const uint32_t* __restrict__ pslot) {
+// LINES: the root cache's line blocks are on: a lane may replay H(m)'s lines or fill a block.  Two
+// kernels, not a flag: with the lines off the call runs k_verify_fused, the kernel it ran before there were lines.
+template <bool LINES>
+__device__ __forceinline__ void verify_fused_lane(const uint8_t* __restrict__ pks, const uint8_t* __restrict__ msgs,
+                                                  const uint64_t* __restrict__ offs, const uint8_t* __restrict__ sigs,
+                                                  uint64_t n, int32_t* __restrict__ status, keycache kc, rootcache rc,
+                                                  const uint32_t* __restrict__ perm,
+                                                  const uint32_t* __restrict__ pslot) {
   const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (j >= n) return;
   // k_root_lookup's order and slots (rootcache.h): lane j takes item perm[j].  perm == nullptr: identity, no root cache.
@@ -41,18 +42,38 @@ __global__ void __launch_bounds__(kBlock) k_verify_fused(const uint8_t* __restri
   BLS_LANE_F12(F);
   // the key's decode goes through the key cache (keycache.h; kc.entries == nullptr: off), H(m) through the root cache
   if (!perm) rc.entries = nullptr;
-  status[i] = op_verify_l_kernel_rc(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i, F, kc, rc,
-                                    perm ? pslot[j] : RC_NONE);
+  status[i] = op_verify_l_kernel_rc<kBlock, LINES>(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i, F, kc,
+                                                   rc, perm ? pslot[j] : RC_NONE);
 #else
   status[i] = op_verify(pks + 48 * i, msgs + o0, (uint32_t)(o1 - o0), sigs + 96 * i);
 #endif
+}
+__global__ void __launch_bounds__(kBlock) k_verify_fused(const uint8_t* __restrict__ pks,
+                                                         const uint8_t* __restrict__ msgs,
+                                                         const uint64_t* __restrict__ offs,
+                                                         const uint8_t* __restrict__ sigs, uint64_t n,
+                                                         int32_t* __restrict__ status, keycache kc, rootcache rc,
+                                                         const uint32_t* __restrict__ perm,
+                                                         const uint32_t* __restrict__ pslot) {
+  verify_fused_lane<false>(pks, msgs, offs, sigs, n, status, kc, rc, perm, pslot);
+}
+__global__ void __launch_bounds__(kBlock) k_verify_fused_lines(const uint8_t* __restrict__ pks,
+                                                               const uint8_t* __restrict__ msgs,
+                                                               const uint64_t* __restrict__ offs,
+                                                               const uint8_t* __restrict__ sigs, uint64_t n,
+                                                               int32_t* __restrict__ status, keycache kc, rootcache rc,
+                                                               const uint32_t* __restrict__ perm,
+                                                               const uint32_t* __restrict__ pslot) {
+  verify_fused_lane<true>(pks, msgs, offs, sigs, n, status, kc, rc, perm, pslot);
 }
 
 // The root cache's lookup stage (rootcache.h), one lane per item, before k_verify_fused: probe the
 // table for the item's root and record its slot (RC_NONE: not cached, or not eligible), and deal the items into an
 // order with the hits at the front and everything else at the back -- one ballot and one atomic per wave on each of
 // two counters, hits counting up from 0, the rest down from n - 1 -- so that at most one wave of the fused kernel
-// mixes hits and misses.  cnt[0], cnt[1]: zeroed before the launch.  partition == 0: identity order.  n < 2^32.
+// mixes hits and misses.  With line blocks on (rc.lines) the front is the hits whose entry names a
+// block inside the pool, the lanes that will replay, and a hit without one sits with the misses: it runs the same
+// full loop as they do.  cnt[0], cnt[1]: zeroed before the launch.  partition == 0: identity order.  n < 2^32.
 // It ends before the fused kernel of its call starts, so a call never hits on its own inserts.
 __global__ void __launch_bounds__(kBlock) k_root_lookup(const uint8_t* __restrict__ msgs,
                                                         const uint64_t* __restrict__ offs, uint64_t n, rootcache rc,
@@ -62,18 +83,19 @@ __global__ void __launch_bounds__(kBlock) k_root_lookup(const uint8_t* __restric
   if (i >= n) return;
   const uint64_t o0 = offs[i], o1 = offs[i + 1];
   const bool eligible = o1 - o0 == RC_MSG_BYTES;
-  uint32_t slot = RC_NONE;
+  uint32_t slot = RC_NONE, e_lines = 0;
   if (eligible) {
     uint32_t tag[8];
     rc_tag_from_msg(tag, msgs + o0);
-    slot = rc_find(rc, tag);
+    slot = rc_find(rc, tag, &e_lines);
   }
   const bool hit = slot != RC_NONE;
+  const bool front = hit && (!rc.lines || (e_lines != 0 && e_lines - 1 < rc.blocks));
   rc_count(rc, 0, hit);
   rc_count(rc, 1, eligible && !hit);
   uint64_t pos = i;
   if (partition) {
-    const uint64_t act = __ballot(1), mh = __ballot(hit), mr = act & ~mh;
+    const uint64_t act = __ballot(1), mh = __ballot(front), mr = act & ~mh;
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     uint32_t bh = 0, br = 0;
     if (lane == (uint32_t)(__ffsll((unsigned long long)act) - 1)) {
@@ -83,7 +105,7 @@ __global__ void __launch_bounds__(kBlock) k_root_lookup(const uint8_t* __restric
     bh = __builtin_amdgcn_readfirstlane(bh);  // the first active lane's: the one that took the ranges
     br = __builtin_amdgcn_readfirstlane(br);
     const uint64_t below = ((uint64_t)1 << lane) - 1;
-    pos = hit ? (uint64_t)bh + __popcll(mh & below) : n - 1 - ((uint64_t)br + __popcll(mr & below));
+    pos = front ? (uint64_t)bh + __popcll(mh & below) : n - 1 - ((uint64_t)br + __popcll(mr & below));
   }
   if (pos >= n) return;  // cannot happen with zeroed counters; never write outside perm
   perm[pos] = (uint32_t)i;

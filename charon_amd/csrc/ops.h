@@ -52,8 +52,13 @@ BLS_HD BLS_CALL int pairing_check_verify_sig(const g1a& pk, const g2a& hm, const
 #define BLS_VERIFY_L_CALL BLS_CALL
 #endif
 // INL: the Miller loop inlined here (k_verify_fused's kernel-inlined chain, op_verify_l_kernel) or called.
-template <int S, bool INL>
-BLS_HD BLS_INLINE int pairing_check_verify_sig_l_body(const g1a& pk, const g2a& hm, const g2a& sig, const f12l<S> F) {
+// LINES (k_verify_fused_lines alone): `plan` names a line block of H(m) to replay in place of the first pair's steps, or one
+// to fill while the full loop runs (rootcache.h); a replayed block that fails its check is followed by the full loop.
+// Each branch raises its own counter (plan->lctr: replays used, replays discarded, blocks published) where it ends, so
+// that nothing of the plan stays live across the loop that follows.
+template <int S, bool INL, bool LINES = false>
+BLS_HD BLS_INLINE int pairing_check_verify_sig_l_body(const g1a& pk, const g2a& hm, const g2a& sig, const f12l<S> F,
+                                                    const rl_plan* plan = nullptr) {
   g1a P1;
   P1.x = G1_GEN_X;
   P1.y = G1_NEG_GEN_Y;
@@ -61,7 +66,24 @@ BLS_HD BLS_INLINE int pairing_check_verify_sig_l_body(const g1a& pk, const g2a& 
   bool in_g2;
   {
     g2j T1;
-    if (INL)
+    if (LINES) {
+      bool done = false;
+      if (rl_wave_all(plan->replay != nullptr)) {  // per wave (rootcache.h): one loop per wave, never two
+        done = miller_loop_2_l_replay<S>(f, F, pk, sig, &T1, plan->replay, plan->seed);
+        rl_count(plan->lctr, RL_CTR_HITS, done);
+        rl_count(plan->lctr, RL_CTR_BAD, !done);
+      }
+      if (!done && rl_wave_any(plan->record != nullptr)) {  // the first pair's steps write their lines out
+        rl_recorder rec{plan->record, plan->seed};         // (a lane without a block to fill: p == nullptr)
+        miller_loop_2_l_body<S, true>(f, F, pk, hm, P1, sig, &T1, rec);
+        if (plan->record) {
+          rl_publish(*plan, rec.h);
+          rl_count(plan->lctr, RL_CTR_PUBLISHED, true);
+        }
+      } else if (!done) {
+        miller_loop_2_l_body<S, true>(f, F, pk, hm, P1, sig, &T1);
+      }
+    } else if (INL)
       miller_loop_2_l_body<S, true>(f, F, pk, hm, P1, sig, &T1);
     else
       miller_loop_2_l<S, true>(f, F, pk, hm, P1, sig, &T1);

@@ -23,10 +23,26 @@ struct g1_pair_in {  // P in affine coordinates, or is_inf
 
 // r = f^((p^12-1)/r * 3)
 
+// A step hands each of its line's three Fp2 values, before the scaling by P's coordinates, to a sink as it is made
+// (k = 1, 2, 0 in that order; rootcache.h's line blocks).  The default sink does nothing, and then the step is the
+// code it was without one.
+#if defined(__HIPCC__)
+#define BLS_MEMBER __forceinline__
+#else
+#define BLS_MEMBER inline
+#endif
+
+struct line_sink_none {
+  BLS_HD BLS_MEMBER void put(int, const fp2&) const {}
+  BLS_HD BLS_MEMBER void next() const {}  // the line is complete
+};
+
 // The products are asm statements the compiler does not reorder, so the source order is the schedule: each temporary
 // dies soon after it is made (peak: five Fp2 temporaries and the line coefficients; computing A..J first kept eight
 // live, and the Miller loop spilled them: 16 % fewer scratch instructions in the loop body).
-BLS_HD BLS_INLINE void miller_dbl_step_inl(g2j& T_in, fp2& g0, fp2& g1, fp2& h1, const fp& xp_in, const fp& yp_in) {
+template <class SINK = line_sink_none>
+BLS_HD BLS_INLINE void miller_dbl_step_inl(g2j& T_in, fp2& g0, fp2& g1, fp2& h1, const fp& xp_in, const fp& yp_in,
+                                         SINK&& sink = SINK()) {
   const fp xp = xp_in;
   const fp yp = yp_in;
   g2j T = T_in;
@@ -37,6 +53,7 @@ BLS_HD BLS_INLINE void miller_dbl_step_inl(g2j& T_in, fp2& g0, fp2& g1, fp2& h1,
     fp2 J3;
     fp2_add(J3, t, t);
     fp2_add(J3, J3, t);
+    sink.put(1, J3);
     fp2_mul_fp(g1, J3, xp);  // g1 = 3 X^2 x_P
   }
   fp2_mul(A, T.x, T.y);
@@ -48,7 +65,9 @@ BLS_HD BLS_INLINE void miller_dbl_step_inl(g2j& T_in, fp2& g0, fp2& g1, fp2& h1,
   fp2_sqr(B, T.y);
   fp2_sub(H, H, B);
   fp2_sub(H, H, C);  // H = 2YZ
+  sink.put(2, H);
   fp2_sub(g0, E, B);  // g0 = 3b' Z^2 - Y^2
+  sink.put(0, g0);
   fp2_mul_fp(h1, H, yp);
   fp2_neg(h1, h1);  // h1 = -2YZ y_P
   fp2_mul(T.z, B, H);  // Z3 = B H
@@ -70,20 +89,24 @@ BLS_HD BLS_INLINE void miller_dbl_step_inl(g2j& T_in, fp2& g0, fp2& g1, fp2& h1,
 BLS_HD BLS_MILLER_CALL void miller_dbl_step(g2j& T_in, fp2& g0, fp2& g1, fp2& h1, const fp& xp_in, const fp& yp_in) { miller_dbl_step_inl(T_in, g0, g1, h1, xp_in, yp_in); }
 
 // Low-liveness order as in the doubling step: the line coefficients first, then each temporary consumed right away.
+template <class SINK = line_sink_none>
 BLS_HD BLS_INLINE void miller_add_step_inl(g2j& T_in, fp2& g0, fp2& g1, fp2& h1, const g2a& Q_in, const fp& xp_in,
-                                         const fp& yp_in) {
+                                         const fp& yp_in, SINK&& sink = SINK()) {
   const fp xp = xp_in;
   const fp yp = yp_in;
   g2j T = T_in;
   fp2 theta, lambda, t, u;
   fp2_mul(t, Q_in.y, T.z);
   fp2_sub(theta, T.y, t);  // theta = Y - y2 Z
+  sink.put(1, theta);
   fp2_mul(t, Q_in.x, T.z);
   fp2_sub(lambda, T.x, t);  // lambda = X - x2 Z
+  sink.put(2, lambda);
   // line
   fp2_mul(t, theta, Q_in.x);
   fp2_mul(u, lambda, Q_in.y);
   fp2_sub(g0, t, u);
+  sink.put(0, g0);
   fp2_mul_fp(g1, theta, xp);
   fp2_neg(g1, g1);
   fp2_mul_fp(h1, lambda, yp);

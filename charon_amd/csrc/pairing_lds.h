@@ -17,6 +17,7 @@
 // that only changes which temporaries hold them (tests/test_host_arith.py compares f and the statuses on the host).
 #pragma once
 #include "pairing.h"
+#include "rootcache.h"
 
 namespace bls {
 
@@ -27,12 +28,6 @@ namespace bls {
 #endif
 
 typedef uint32_t u32x4 __attribute__((vector_size(16)));  // one ds_read_b128 / ds_write_b128
-
-#if defined(__HIPCC__)
-#define BLS_MEMBER __forceinline__
-#else
-#define BLS_MEMBER inline
-#endif
 
 template <int S>
 struct f12l {
@@ -383,9 +378,24 @@ BLS_HD BLS_INLINE void park_agpr(T& x) {
 // it), and k_verify_fused inlines the body into the kernel itself (ops.h op_verify_l_kernel), where no callee-saved
 // register set applies: the loop then spills to all 256 AGPRs before scratch (225 scratch instructions per doubling
 // iteration instead of 275, C2 +0.5 %).
-template <int S, bool P1_NEG_GEN = false>
+// The first pair's steps hand their raw line values to `sink` (pairing.h; rootcache.h's line blocks): rl_recorder for
+// k_verify_fused's lanes that fill a block (ops.h; p == nullptr records nothing), and no sink for every other caller.
+struct rl_recorder {
+  uint32_t* p;  // the line being written; nullptr: this lane does not record
+  uint64_t h;   // the block's check so far
+  BLS_HD BLS_MEMBER void put(int k, const fp2& v) {
+    if (!p) return;
+    rl_store_words(p + 24 * k, &v.c0.v[0], 24);
+    h = rl_fold(h, &v.c0.v[0], 24);
+  }
+  BLS_HD BLS_MEMBER void next() {
+    if (p) p += RL_LINE_WORDS;
+  }
+};
+
+template <int S, bool P1_NEG_GEN = false, class SINK = line_sink_none>
 BLS_HD BLS_INLINE void miller_loop_2_l_body(fp12& f_out, const f12l<S> F, const g1a& P0_in, const g2a& Q0,
-                                          const g1a& P1_in, const g2a& Q1, g2j* T1_out) {
+                                          const g1a& P1_in, const g2a& Q1, g2j* T1_out, SINK&& sink = SINK()) {
   g1a P0 = P0_in;
   g1a P1;
   if (P1_NEG_GEN) {
@@ -404,11 +414,13 @@ BLS_HD BLS_INLINE void miller_loop_2_l_body(fp12& f_out, const f12l<S> F, const 
   {
     fp12 f;
     fp2 a0, a1, ah, g0, g1, h1;
-    miller_dbl_step_inl(T0, a0, a1, ah, P0.x, P0.y);
+    miller_dbl_step_inl(T0, a0, a1, ah, P0.x, P0.y, sink);
+    sink.next();
     miller_dbl_step_inl(T1, g0, g1, h1, P1.x, P1.y);
     fp12_line_pair(f, a0, a1, ah, g0, g1, h1);
     F.st12(f);
-    miller_add_step_inl(T0, a0, a1, ah, Q0, P0.x, P0.y);  // bit 62 of |x| is set
+    miller_add_step_inl(T0, a0, a1, ah, Q0, P0.x, P0.y, sink);  // bit 62 of |x| is set
+    sink.next();
     miller_add_step_inl(T1, g0, g1, h1, Q1, P1.x, P1.y);
     fp12_mul_line2_l(F, a0, a1, ah, g0, g1, h1);
   }
@@ -422,7 +434,8 @@ BLS_HD BLS_INLINE void miller_loop_2_l_body(fp12& f_out, const f12l<S> F, const 
 #endif
     fp12_sqr_l(F);
     fp2 a0, a1, ah, g0, g1, h1;
-    BLS_ML_DBL(T0, a0, a1, ah, P0.x, P0.y);
+    BLS_ML_DBL(T0, a0, a1, ah, P0.x, P0.y, sink);
+    sink.next();
 #if BLS_ML_PARK & 2
     park_agpr(T0);
     park_agpr(a0);
@@ -432,7 +445,8 @@ BLS_HD BLS_INLINE void miller_loop_2_l_body(fp12& f_out, const f12l<S> F, const 
     BLS_ML_DBL(T1, g0, g1, h1, P1.x, P1.y);
     fp12_mul_line2_l(F, a0, a1, ah, g0, g1, h1);
     if ((X_ABS >> bit) & 1ull) {
-      miller_add_step_inl(T0, a0, a1, ah, Q0, P0.x, P0.y);
+      miller_add_step_inl(T0, a0, a1, ah, Q0, P0.x, P0.y, sink);
+      sink.next();
       miller_add_step_inl(T1, g0, g1, h1, Q1, P1.x, P1.y);
       fp12_mul_line2_l(F, a0, a1, ah, g0, g1, h1);
     }
@@ -441,6 +455,103 @@ BLS_HD BLS_INLINE void miller_loop_2_l_body(fp12& f_out, const f12l<S> F, const 
   F.ld12(f);
   fp12_conj(f_out, f);
   if (T1_out) *T1_out = T1;
+}
+
+// The first pair's line at P0 from a block's raw values (rootcache.h): the same fp2_mul_fp / fp2_neg on the same
+// canonical words as the steps in pairing.h, so a0, a1, ah are theirs bit for bit.
+BLS_HD BLS_INLINE void rl_line_dbl(fp2& a0, fp2& a1, fp2& ah, const uint32_t w[RL_LINE_WORDS], const g1a& P0) {
+  fp2 J3, H;
+  for (int k = 0; k < 12; ++k) {
+    a0.c0.v[k] = w[k], a0.c1.v[k] = w[12 + k];
+    J3.c0.v[k] = w[24 + k], J3.c1.v[k] = w[36 + k];
+    H.c0.v[k] = w[48 + k], H.c1.v[k] = w[60 + k];
+  }
+  fp2_mul_fp(a1, J3, P0.x);
+  fp2_mul_fp(ah, H, P0.y);
+  fp2_neg(ah, ah);
+}
+BLS_HD BLS_INLINE void rl_line_add(fp2& a0, fp2& a1, fp2& ah, const uint32_t w[RL_LINE_WORDS], const g1a& P0) {
+  fp2 theta, lambda;
+  for (int k = 0; k < 12; ++k) {
+    a0.c0.v[k] = w[k], a0.c1.v[k] = w[12 + k];
+    theta.c0.v[k] = w[24 + k], theta.c1.v[k] = w[36 + k];
+    lambda.c0.v[k] = w[48 + k], lambda.c1.v[k] = w[60 + k];
+  }
+  fp2_mul_fp(a1, theta, P0.x);
+  fp2_neg(a1, a1);
+  fp2_mul_fp(ah, lambda, P0.y);
+}
+
+// Verify's loop (P1 = -g1, Q1 = sig) with the first pair's lines replayed from the block `blk` instead of walked from
+// H(m): no T0, no Q0, none of that pair's doubling and addition steps.  A line's 288 bytes are loaded right where they
+// are used, after the second pair's step: loaded before it they do not stay in registers across it, and the spill of
+// each group of loads waited for the memory four or five times per line (22.85 ms per launch against 22.1 for the
+// work left; asking for one word of each of the line's cache lines before that step changed nothing; DESIGN.md
+// 4.11.1).  Returns whether the block's check value holds over the words that were used;
+// on false f_out and T1_out mean nothing and the caller runs the full loop.
+template <int S>
+BLS_HD BLS_INLINE bool miller_loop_2_l_replay(fp12& f_out, const f12l<S> F, const g1a& P0_in, const g2a& Q1,
+                                            g2j* T1_out, const uint32_t* blk, uint64_t seed) {
+  g1a P0 = P0_in;
+  g1a P1;
+  P1.x = G1_GEN_X;
+  P1.y = G1_NEG_GEN_Y;
+  g2j T1;
+  T1.x = Q1.x;
+  T1.y = Q1.y;
+  fp2_set_one(T1.z);
+  uint64_t h = seed;
+  const uint32_t* p = blk;
+  uint32_t chk[4];
+  rl_load_check(chk, blk);
+  {
+    fp12 f;
+    fp2 a0, a1, ah, g0, g1, h1;
+    uint32_t w[RL_LINE_WORDS];
+    miller_dbl_step_inl(T1, g0, g1, h1, P1.x, P1.y);
+    rl_load_line(w, p);
+    p += RL_LINE_WORDS;
+    h = rl_fold_line(h, w);
+    rl_line_dbl(a0, a1, ah, w, P0);
+    fp12_line_pair(f, a0, a1, ah, g0, g1, h1);
+    F.st12(f);
+    miller_add_step_inl(T1, g0, g1, h1, Q1, P1.x, P1.y);  // bit 62 of |x| is set
+    rl_load_line(w, p);
+    p += RL_LINE_WORDS;
+    h = rl_fold_line(h, w);
+    rl_line_add(a0, a1, ah, w, P0);
+    fp12_mul_line2_l(F, a0, a1, ah, g0, g1, h1);
+  }
+  for (int bit = 61; bit >= 0; --bit) {
+#if BLS_ML_PARK & 1
+    park_agpr(T1);
+#endif
+#if BLS_ML_PARK & 4
+    park_agpr(P0);
+#endif
+    fp12_sqr_l(F);
+    fp2 a0, a1, ah, g0, g1, h1;
+    uint32_t w[RL_LINE_WORDS];
+    BLS_ML_DBL(T1, g0, g1, h1, P1.x, P1.y);
+    rl_load_line(w, p);
+    p += RL_LINE_WORDS;
+    h = rl_fold_line(h, w);
+    rl_line_dbl(a0, a1, ah, w, P0);
+    fp12_mul_line2_l(F, a0, a1, ah, g0, g1, h1);
+    if ((X_ABS >> bit) & 1ull) {
+      miller_add_step_inl(T1, g0, g1, h1, Q1, P1.x, P1.y);
+      rl_load_line(w, p);
+      p += RL_LINE_WORDS;
+      h = rl_fold_line(h, w);
+      rl_line_add(a0, a1, ah, w, P0);
+      fp12_mul_line2_l(F, a0, a1, ah, g0, g1, h1);
+    }
+  }
+  fp12 f;
+  F.ld12(f);
+  fp12_conj(f_out, f);
+  if (T1_out) *T1_out = T1;
+  return rl_check_ok(h, chk[0], chk[1]);
 }
 template <int S, bool P1_NEG_GEN = false>
 BLS_HD BLS_MILLER_L_CALL void miller_loop_2_l(fp12& f_out, const f12l<S> F, const g1a& P0_in, const g2a& Q0, const g1a& P1_in,

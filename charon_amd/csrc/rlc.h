@@ -292,25 +292,41 @@ BLS_HD BLS_INLINE int tv_key_lane(g1a& lpk, uint64_t k, uint64_t T, const int32_
 // nothing).  A recorded slot's entry is loaded and verified against the message's own bytes; it then stands for
 // hash_to_g2 + jac_to_aff.  Otherwise the message is hashed as ever, and an eligible one (32 bytes) is published.
 // rc.entries == nullptr: the cache is off.
-BLS_HD BLS_CALL void verify_hm_rc(g2a& hm, const uint8_t* msg, uint32_t msg_len, const rootcache& rc, uint32_t slot) {
+// plan (when given; zeroed by the caller's rl_plan{}): what the lane does about H(m)'s line block (rootcache.h) -- a hit
+// whose entry names a block replays it, the lane that wins the insert takes a block to fill if the pool has one left,
+// and everything else leaves the plan empty.
+BLS_HD BLS_CALL void verify_hm_rc(g2a& hm, const uint8_t* msg, uint32_t msg_len, const rootcache& rc, uint32_t slot,
+                                  rl_plan* plan = nullptr) {
   const bool eligible = rc.entries && msg_len == RC_MSG_BYTES;
   uint32_t tag[8];
   if (eligible) rc_tag_from_msg(tag, msg);
-  bool ins = false;
-  if (!(eligible && slot != RC_NONE && rc_get_slot(rc, slot, tag, &hm.x.c0.v[0]))) {
+  bool ins = false, full = false;
+  uint32_t e_lines = 0;
+  if (eligible && slot != RC_NONE && rc_get_slot(rc, slot, tag, &hm.x.c0.v[0], &e_lines)) {
+    if (plan) rl_plan_hit(*plan, rc, e_lines, rc_tag_hash(tag));
+  } else {
     g2j hj;
     hash_to_g2(hj, msg, msg_len, DST_POP, 43);
     const bool inf = jac_is_inf(hj);
     jac_to_aff(hm, hj);
-    if (eligible && !inf) ins = rc_insert(rc, tag, &hm.x.c0.v[0]);
+    if (eligible && !inf) {
+      const uint32_t s = rc_insert_slot(rc, tag, &hm.x.c0.v[0]);
+      ins = s != RC_NONE;
+      if (ins && plan && rc.lines) {
+        rl_plan_insert(*plan, rc, s, rc_tag_hash(tag));
+        full = !plan->record;
+      }
+    }
   }
   if (rc.entries) rc_count(rc, 2, ins);
+  if (rc.entries && rc.lines && plan) rl_count(rc.lctr, RL_CTR_FULL, full);
 }
 
 // k_verify_fused's form (ops.h op_verify_l_kernel: the same statuses in the same order as op_verify_l_rest, the whole
 // chain down to the Miller loop inlined into the kernel) with the key's decode behind the key cache and H(m) behind
 // the root cache: hits and misses of either join the same chain.
-template <int S>
+// LINES (k_verify_fused_lines): H(m)'s line block is replayed or filled where the root cache says so.
+template <int S, bool LINES = true>
 BLS_HD BLS_INLINE int op_verify_l_kernel_rc(const uint8_t* pk48, const uint8_t* msg, uint32_t msg_len,
                                             const uint8_t* sig96, const f12l<S> F, const keycache& kc,
                                             const rootcache& rc, uint32_t slot) {
@@ -322,8 +338,13 @@ BLS_HD BLS_INLINE int op_verify_l_kernel_rc(const uint8_t* pk48, const uint8_t* 
   if (ds == DEC_BAD) return HIPBLS_ERR_SIGNATURE;
   if (dp == DEC_INF || ds == DEC_INF) return verify_inf_status(ds, sig);
   g2a hm;
-  verify_hm_rc(hm, msg, msg_len, rc, slot);
-  return pairing_check_verify_sig_l_body<S, true>(pk, hm, sig, F);
+  if (!LINES) {
+    verify_hm_rc(hm, msg, msg_len, rc, slot);
+    return pairing_check_verify_sig_l_body<S, true>(pk, hm, sig, F);
+  }
+  rl_plan plan{};
+  verify_hm_rc(hm, msg, msg_len, rc, slot, &plan);
+  return pairing_check_verify_sig_l_body<S, true, true>(pk, hm, sig, F, &plan);
 }
 
 // tbls.Verify with the public key taken from the table (same statuses as op_verify); the Miller loop's f in LDS.

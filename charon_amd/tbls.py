@@ -96,6 +96,8 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_keycache_stats": ([u64p, u64p, u64p], ctypes.c_int),
         "hipbls_rootcache_config": ([u64], ctypes.c_int),
         "hipbls_rootcache_stats": ([u64p, u64p, u64p, u64p], ctypes.c_int),
+        "hipbls_rootcache_lines_config": ([u64], ctypes.c_int),
+        "hipbls_rootcache_lines_stats": ([u64p, u64p, u64p, u64p], ctypes.c_int),
         "hipbls_abi_version": ([], ctypes.c_int),
         "hipbls_init": ([ctypes.c_int], ctypes.c_int),
         "hipbls_device_count": ([], ctypes.c_int),
@@ -177,6 +179,7 @@ def exported_symbols() -> List[str]:
         "hipbls_keycache_config", "hipbls_keycache_stats", "hipbls_hcache_prefetch",
         "hipbls_verify_aggregate_batch_keys", "hipbls_verify_aggregate_batch_keys_device",
         "hipbls_rootcache_config", "hipbls_rootcache_stats",
+        "hipbls_rootcache_lines_config", "hipbls_rootcache_lines_stats",
         "hipbls_sign_batch_ct", "hipbls_secret_to_public_key_batch_ct", "hipbls_sign_batch_ct_device",
         "hipbls_secret_to_public_key_batch_ct_device",
         "hipbls_threshold_split_batch_ct", "hipbls_recover_secret_batch_ct",
@@ -834,6 +837,18 @@ class HipBLS:
         a, b, c, d = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self.lib.hipbls_rootcache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)),
                self.lib)
+        return a.value, b.value, c.value, d.value
+
+    def rootcache_lines_config(self, blocks: Optional[int] = None) -> None:
+        """Size the root cache's line pool to `blocks` blocks (0 = lines off, None = the default, half the slots);
+        empties the root cache as well."""
+        _check(self.lib.hipbls_rootcache_lines_config(2 ** 64 - 1 if blocks is None else blocks), self.lib)
+
+    def rootcache_lines_stats(self) -> Tuple[int, int, int, int]:
+        """(line_hits, blocks_published, pool_full, check_failures) since the last config, summed over contexts."""
+        a, b, c, d = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self.lib.hipbls_rootcache_lines_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                     ctypes.byref(d)), self.lib)
         return a.value, b.value, c.value, d.value
 
     # ---------------------------------------------------------------- pairing-check layout

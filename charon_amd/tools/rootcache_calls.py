@@ -1,14 +1,17 @@
-"""Single wire-format Verify calls against the root cache (DESIGN.md 4.11): the cold call and mixed calls.
+"""Single wire-format Verify calls against the root cache (DESIGN.md 4.11, 4.11.1): the cold call and mixed calls.
 
     [HIPBLS_ROOTCACHE_PARTITION=0] python3 charon_amd/tools/rootcache_calls.py [--n 65536,131072]
-        [--warm 0,50,90,100] [--repeats 3] [--slots 1048576]
+        [--warm 0,50,90,100] [--repeats 3] [--slots 1048576] [--lines on,off,hwarm]
 
 Every row is one hipbls_verify_batch_device call of n valid items over n distinct 32-byte roots between two HIP events
 on the call's stream.  Before each clocked call the root cache is emptied (hipbls_rootcache_config, outside the clock)
 and one unclocked call over the roots that are to be warm fills it; warm roots are spread evenly over the batch
 (i * pct // 100 steps), so that in the items' own order every wave mixes hits and misses.  warm = 0 is the cold call;
 the "off" row is the same call with the cache off.  The key cache is warm throughout.  HIPBLS_ROOTCACHE_PARTITION is
-read at init, so partition on and off are two processes.  Prints one JSON object per row, then a summary object.
+read at init, so partition on and off are two processes.  --lines names the line-block states to run, each a row of
+its own: "on" (the default pool, half the slots: warm roots replay, new ones record), "off" (no pool) and "hwarm" (a
+pool of one block, so that the warm roots have H(m) cached and no lines: the state a full pool leaves).  Prints one
+JSON object per row, then a summary object.
 """
 import argparse
 import ctypes
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--slots", type=int, default=1 << 20)
     ap.add_argument("--keys", type=int, default=4096)
+    ap.add_argument("--lines", default="on,off,hwarm")
     args = ap.parse_args()
     import torch
     from charon_amd import build as hb
@@ -92,25 +96,33 @@ def main():
             off.append(call(everything, True))
         rows.append({"n": n, "warm_pct": None, "cache": "off", "ms": [round(x, 3) for x in off]})
         print(json.dumps(rows[-1]), flush=True)
-        for pct in [int(x) for x in args.warm.split(",")]:
+        for pct, lines in [(int(x), m) for x in args.warm.split(",") for m in args.lines.split(",")]:
             warm = [i for i in everything if (i + 1) * pct // 100 != i * pct // 100]
-            ms, hits, inserts, fused_ms, lookup_ms = [], [], [], [], []
+            if lines == "hwarm" and not warm:
+                continue  # nothing is warm: the "on" row
+            ms, hits, inserts, fused_ms, lookup_ms, line_hits, published = [], [], [], [], [], [], []
             for _ in range(args.repeats):
                 impl.rootcache_config(args.slots)
+                impl.rootcache_lines_config({"on": None, "off": 0, "hwarm": 1}[lines])
                 if warm:
                     call(warm, False)
-                s0 = impl.rootcache_stats()
+                s0, l0 = impl.rootcache_stats(), impl.rootcache_lines_stats()
                 lib.hipbls_kernel_timing_reset()
                 ms.append(call(everything, True))
-                s1 = impl.rootcache_stats()
+                s1, l1 = impl.rootcache_stats(), impl.rootcache_lines_stats()
                 hits.append(s1[0] - s0[0])
                 inserts.append(s1[2] - s0[2])
+                line_hits.append(l1[0] - l0[0])
+                published.append(l1[1] - l0[1])
+                assert l1[3] == 0, l1
                 fused_ms.append(round(kernel_ms(b"verify"), 3))
                 lookup_ms.append(round(kernel_ms(b"root_lookup"), 3))
-            rows.append({"n": n, "warm_pct": pct, "cache": "on", "partition": partition, "warm_roots": len(warm),
-                         "hits": hits, "inserts": inserts, "ms": [round(x, 3) for x in ms],
+            rows.append({"n": n, "warm_pct": pct, "cache": "on", "lines": lines, "partition": partition,
+                         "warm_roots": len(warm), "hits": hits, "inserts": inserts, "line_hits": line_hits,
+                         "blocks_published": published, "ms": [round(x, 3) for x in ms],
                          "k_verify_fused_ms": fused_ms, "k_root_lookup_ms": lookup_ms})
             print(json.dumps(rows[-1]), flush=True)
+    impl.rootcache_lines_config(None)
     print(json.dumps({"tool": "rootcache_calls", "partition": partition, "slots": args.slots, "repeats": args.repeats,
                       "rows": rows}))
 

@@ -392,6 +392,20 @@ int hipbls_keycache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts);
 int hipbls_rootcache_config(uint64_t slots);
 int hipbls_rootcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, uint64_t* rollovers);
 
+/* Line blocks of the root cache: beside H(m), the lane that publishes a root also records the 68 Miller-loop lines of
+ * e(., H(m)) before their scaling by the key (19,712 B per root, in a pool of `blocks` blocks), and a later Verify of
+ * that root replays them instead of walking H(m) through 63 doublings and 5 additions; the replayed words carry a
+ * check value bound to the root, and a block that fails it is followed by the full loop.  Statuses are unchanged.
+ * Default: half the root cache's slots (131,072 blocks, about 2.4 GiB per context, allocated by the first batch that
+ * takes the one-lane route), or HIPBLS_ROOTCACHE_LINES; 0 turns the lines off, at most 2^22, and UINT64_MAX asks for
+ * the default again.  A full pool publishes H(m) alone.  hipbls_rootcache_lines_config acts as
+ * hipbls_rootcache_config does and also empties the root cache and its counters.  Stats are summed over contexts, since the last config of either kind: Verifies that replayed a
+ * block, blocks published, roots published without a block because the pool was full, replays discarded by the
+ * check.  hipbls_rootcache_lines_stats waits for the device under each context's lock: a diagnostic. */
+int hipbls_rootcache_lines_config(uint64_t blocks);
+int hipbls_rootcache_lines_stats(uint64_t* line_hits, uint64_t* blocks_published, uint64_t* pool_full,
+                                 uint64_t* check_failures);
+
 /* ------------------------------------------- device-resident variants (inputs already in HBM) ---- */
 /* Same semantics; every pointer is a device pointer; work is enqueued on `stream` (a hipStream_t,
  * NULL = the library's own non-blocking stream of that device, which is NOT ordered with the caller's default
