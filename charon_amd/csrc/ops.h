@@ -89,9 +89,9 @@ BLS_HD BLS_INLINE int pairing_check_verify_sig_l_body(const g1a& pk, const g2a& 
       miller_loop_2_l<S, true>(f, F, pk, hm, P1, sig, &T1);
     in_g2 = g2_subgroup_from_miller(T1, sig);
   }
-  final_exp_l(f, f, F);  // in place: one Fp12 less in this frame (final_exponentiation_l allows r == f_in)
+  const bool one = final_exp_l_is_one(f, F);  // in place, or compared without the last product (pairing_lds.h BLS_FE_CMP)
   if (!in_g2) return HIPBLS_ERR_SIGNATURE;
-  return fp12_is_one(f) ? HIPBLS_OK : HIPBLS_ERR_VERIFY;
+  return one ? HIPBLS_OK : HIPBLS_ERR_VERIFY;
 }
 template <int S>
 BLS_HD BLS_VERIFY_L_CALL int pairing_check_verify_sig_l(const g1a& pk, const g2a& hm, const g2a& sig, const f12l<S> F) {

@@ -599,37 +599,65 @@ BLS_HD BLS_INLINE void fp12_mul_l(const f12l<S>& F, const fp12& b) {
 // Returns true, leaving r untouched, in the degenerate case: the caller then takes the Granger-Scott exponentiation
 // (fp12_cyc_exp_xabs_l), so that rarely used call chain adds to the caller's stack depth, not to this one's -- every
 // kernel's private segment is sized by its deepest chain (~3 KB less per lane here).
+//
+// Hybrid (BLS_FE_HYBRID): compressed squarings run up to bit 57 only, and a^(2^60), a^(2^62), a^(2^63)
+// come from the decompressed a^(2^57) by 3 + 2 + 1 Granger-Scott squarings.  A compressed squaring is 12 Fp products
+// and a Granger-Scott one 18, so each squaring taken uncompressed costs 6 products more, and each saved state not
+// decompressed saves its cyc_z1_parts, prefix product, two back-substitution products and cyc_decompress, about 27
+// products.  Splitting at 57 trades 6 squarings for 3 decompressions (6 x 6 - 3 x 27 = -45 products); at 60 it is
+// 3 squarings for 2 (-36), at 62 one for one (-21), and at 48 it would be 15 squarings for 4 (-18).
+#ifndef BLS_FE_HYBRID
+#define BLS_FE_HYBRID 1
+#endif
+constexpr int KAR_STATES = BLS_FE_HYBRID ? 3 : 6;  // saved compressed states: a^(2^k) for k = 16, 48, 57[, 60, 62, 63]
+// The power from its saved states; true (r untouched) when a denominator vanishes at any of them.
 template <int S>
-BLS_HD BLS_CALL bool fp12_cyc_exp_xabs_karabina_l(fp12& r, const fp12& a_in, const f12l<S> F) {
-  static_assert(X_ABS == 0xd201000000010000ull, "the squaring counts below are |x|'s set bits");
-  cyc_c st[6];  // a^(2^k) for k = 16, 48, 57, 60, 62, 63
-  cyc_c c;
-  c.z2 = a_in.c1.c0;
-  c.z3 = a_in.c0.c2;
-  c.z4 = a_in.c0.c1;
-  c.z5 = a_in.c1.c2;
-  cyc_sqr_run(c, 16);
-  st[0] = c;
-  cyc_sqr_run(c, 32);
-  st[1] = c;
-  cyc_sqr_run(c, 9);
-  st[2] = c;
-  cyc_sqr_run(c, 3);
-  st[3] = c;
-  cyc_sqr_run(c, 2);
-  st[4] = c;
-  cyc_sqr_run(c, 1);
-  st[5] = c;
-  fp2 num[6], den[6], pre[6];
+BLS_HD BLS_INLINE bool cyc_exp_xabs_from_states_l(fp12& r, const cyc_c* st, const f12l<S>& F) {
+  fp2 num[KAR_STATES], den[KAR_STATES], pre[KAR_STATES];
   int s;
 #pragma unroll 1
-  for (s = 0; s < 6; ++s) cyc_z1_parts(num[s], den[s], st[s]);
+  for (s = 0; s < KAR_STATES; ++s) cyc_z1_parts(num[s], den[s], st[s]);
   pre[0] = den[0];
 #pragma unroll 1
-  for (s = 1; s < 6; ++s) fp2_mul(pre[s], pre[s - 1], den[s]);
-  if (fp2_is_zero(pre[5])) return true;  // practically never: the identity or z2 = z3 = 0 at one of the six powers
+  for (s = 1; s < KAR_STATES; ++s) fp2_mul(pre[s], pre[s - 1], den[s]);
+  // practically never: the identity or z2 = z3 = 0 at one of the saved powers
+  if (fp2_is_zero(pre[KAR_STATES - 1])) return true;
   fp2 inv;
-  fp2_inv(inv, pre[5]);
+  fp2_inv(inv, pre[KAR_STATES - 1]);
+#if BLS_FE_HYBRID
+  // z1 of every state first (into num[]), so that the top state can be decompressed last: nothing but its Fp12 is
+  // live across the uncompressed squarings that follow it
+#pragma unroll 1
+  for (s = KAR_STATES - 1; s >= 0; --s) {
+    fp2 is;
+    if (s > 0) {
+      fp2_mul(is, inv, pre[s - 1]);  // 1 / den[s]
+      fp2_mul(inv, inv, den[s]);
+    } else {
+      is = inv;
+    }
+    fp2_mul(num[s], num[s], is);
+  }
+  // six factors in one loop (one copy of the Fp12 product): a^(2^16), a^(2^48), a^(2^57), then 3, 2 and 1 squarings on
+  fp12 d;
+#pragma unroll 1
+  for (int j = 0; j < 6; ++j) {
+    if (j < 3) {
+      cyc_decompress(d, st[j], num[j]);
+    } else {
+#pragma unroll 1
+      for (int k = j; k < 6; ++k) {
+        fp12 t;
+        fp12_cyclotomic_sqr_body(t, d);
+        d = t;
+      }
+    }
+    if (j == 0)
+      F.st12(d);
+    else
+      fp12_mul_l(F, d);
+  }
+#else
 #pragma unroll 1
   for (s = 5; s >= 0; --s) {
     fp2 is, z1;
@@ -647,8 +675,34 @@ BLS_HD BLS_CALL bool fp12_cyc_exp_xabs_karabina_l(fp12& r, const fp12& a_in, con
     else
       fp12_mul_l(F, d);
   }
+#endif
   F.ld12(r);
   return false;
+}
+template <int S>
+BLS_HD BLS_CALL bool fp12_cyc_exp_xabs_karabina_l(fp12& r, const fp12& a_in, const f12l<S> F) {
+  static_assert(X_ABS == 0xd201000000010000ull, "the squaring counts below are |x|'s set bits");
+  cyc_c st[KAR_STATES];
+  cyc_c c;
+  c.z2 = a_in.c1.c0;
+  c.z3 = a_in.c0.c2;
+  c.z4 = a_in.c0.c1;
+  c.z5 = a_in.c1.c2;
+  cyc_sqr_run(c, 16);
+  st[0] = c;
+  cyc_sqr_run(c, 32);
+  st[1] = c;
+  cyc_sqr_run(c, 9);
+  st[2] = c;
+#if !BLS_FE_HYBRID
+  cyc_sqr_run(c, 3);
+  st[3] = c;
+  cyc_sqr_run(c, 2);
+  st[4] = c;
+  cyc_sqr_run(c, 1);
+  st[5] = c;
+#endif
+  return cyc_exp_xabs_from_states_l(r, st, F);
 }
 template <int S>
 BLS_HD BLS_INLINE void fp12_cyc_exp_xabs_l(fp12& r, const fp12& a_in, const f12l<S>& F) {
@@ -656,8 +710,12 @@ BLS_HD BLS_INLINE void fp12_cyc_exp_xabs_l(fp12& r, const fp12& a_in, const f12l
 }
 
 // final_exponentiation (pairing.h) with the a^|x| powers on fp12_cyc_exp_xabs_karabina_l; F is free scratch here.
-template <int S>
-BLS_HD BLS_CALL void final_exponentiation_l(fp12& r, const fp12& f_in, const f12l<S> F) {
+// CMP: only "is the result one?" is asked (Verify).  The result is t2 m^3 with both factors in the cyclotomic subgroup,
+// where the inverse is the conjugate, so it is one exactly when t2 == conj(m^3): the last Fp12 product is left out and
+// r is not written.  The one f_in whose easy part is not in that subgroup is 0 (Fp12 is a field): there m, t2 and m^3
+// are all 0, the value form returns 0, and the comparison of 0 with 0 must not pass for one -- hence the test of m.
+template <int S, bool CMP>
+BLS_HD BLS_INLINE bool final_exponentiation_l_body(fp12& r, const fp12& f_in, const f12l<S>& F) {
   // The temporaries are scoped so their stack slots can share space: every Fp12 here is passed by address to a real
   // call, so it lives in the frame, and at function scope each one held its own 576 B for the whole function (the
   // frame is part of every verify kernel's private segment).  f_in is read only by the easy part and r written only
@@ -699,9 +757,30 @@ BLS_HD BLS_CALL void final_exponentiation_l(fp12& r, const fp12& f_in, const f12
     fp12 u;
     fp12_cyclotomic_sqr(u, m);
     BLS_FE_MUL(u, u, m);
+    if (CMP) {
+      fp12_conj(u, u);
+      return fp12_eq(t2, u) && !fp12_is_zero(m);
+    }
     BLS_FE_MUL(r, t2, u);
   }
+  return false;
 }
+template <int S>
+BLS_HD BLS_CALL void final_exponentiation_l(fp12& r, const fp12& f_in, const f12l<S> F) {
+  final_exponentiation_l_body<S, false>(r, f_in, F);
+}
+// fp12_is_one(final_exponentiation_l(f)) without the last product
+template <int S>
+BLS_HD BLS_CALL bool final_exp_is_one_l(const fp12& f_in, const f12l<S> F) {
+  fp12 unused;
+  return final_exponentiation_l_body<S, true>(unused, f_in, F);
+}
+// Verify's check takes the comparison only with -DBLS_FE_CMP=1.  It removes 15,552 of a warm lane's 4.64M multiply-adds
+// and measured C2 +7.5 k/s alone and +13.1 k/s beside the hybrid power (profiles/r18/parts_summary.json), in every
+// round but below five times the parent's run-to-run spread (4.4 k/s), so the product keeps the value form.
+#ifndef BLS_FE_CMP
+#define BLS_FE_CMP 0
+#endif
 #ifndef BLS_FE_LDS
 #define BLS_FE_LDS 1
 #endif
@@ -711,6 +790,17 @@ BLS_HD BLS_INLINE void final_exp_l(fp12& r, const fp12& f, const f12l<S>& F) {
   final_exponentiation_l(r, f, F);
 #else
   final_exponentiation(r, f);
+#endif
+}
+// Is f's final exponentiation one?  f is used up: the value form works in place, one Fp12 less in the caller's frame
+// (final_exponentiation_l allows r == f_in).
+template <int S>
+BLS_HD BLS_INLINE bool final_exp_l_is_one(fp12& f, const f12l<S>& F) {
+#if BLS_FE_LDS && BLS_FE_CMP
+  return final_exp_is_one_l(f, F);
+#else
+  final_exp_l(f, f, F);
+  return fp12_is_one(f);
 #endif
 }
 

@@ -149,6 +149,19 @@ BLS_HD BLS_INLINE bool fp12_is_one(const fp12& a) {
   for (int i = 0; i < 12; ++i) eq = eq && fp_eq(x[i], y[i]);
   return eq;
 }
+BLS_HD BLS_INLINE bool fp12_eq(const fp12& a, const fp12& b) {
+  bool eq = true;
+  const fp* x = &a.c0.c0.c0;
+  const fp* y = &b.c0.c0.c0;
+  for (int i = 0; i < 12; ++i) eq = eq && fp_eq(x[i], y[i]);
+  return eq;
+}
+BLS_HD BLS_INLINE bool fp12_is_zero(const fp12& a) {
+  const fp2* x = &a.c0.c0;
+  bool z = true;
+  for (int i = 0; i < 6; ++i) z = z && fp2_is_zero(x[i]);
+  return z;
+}
 BLS_HD BLS_INLINE void fp12_conj(fp12& r, const fp12& a) {
   r.c0 = a.c0;
   fp6_neg(r.c1, a.c1);
