@@ -13,7 +13,8 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    deps = [SRC, os.path.join(HERE, "native", "arith_units.h")]
+    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     deps.append(os.path.join(os.path.dirname(HERE), "include", "hipbls.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -32,16 +33,31 @@ def build():
 
 GU_SRC = os.path.join(HERE, "native", "gpu_units.hip")
 GU_LIB = os.path.join(HERE, "native", "libgpu_units.so")
+GUP_SRC = os.path.join(HERE, "native", "gpu_units_pair.hip")  # the split-Fp2 build (BLS_FP2_PAIR), a sibling library
+GUP_LIB = os.path.join(HERE, "native", "libgpu_units_pair.so")
+AU_HDR = os.path.join(HERE, "native", "arith_units.h")  # the layer dispatchers shared by host_ops.cpp and gpu_units.hip
 
 
 def build_gpu_units():
-    """Test-only device entry points into single kernel building blocks (tests/test_gpu_units.py), gfx950."""
-    deps = [GU_SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    if not os.path.exists(GU_LIB) or any(os.path.getmtime(d) > os.path.getmtime(GU_LIB) for d in deps):
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                               "-I" + CSRC, "-I" + os.path.join(os.path.dirname(HERE), "include"),
-                               "-o", GU_LIB + ".tmp", GU_SRC])
-        os.replace(GU_LIB + ".tmp", GU_LIB)
+    """Test-only device entry points into single kernel building blocks (tests/test_gpu_units.py) and into every
+    arithmetic layer (tests/test_gpu_arith_layers.py), gfx950.  The two libraries compile side by side."""
+    hdrs = [AU_HDR] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    jobs = []
+    for src, out in ((GU_SRC, GU_LIB), (GUP_SRC, GUP_LIB)):
+        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in [src] + hdrs):
+            cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC,
+                   "-I" + os.path.join(os.path.dirname(HERE), "include"), "-o", out + ".tmp", src]
+            jobs.append((subprocess.Popen(cmd), cmd, out))
+    failed = None
+    for proc, cmd, out in jobs:
+        if proc.wait() != 0:
+            failed = failed or subprocess.CalledProcessError(proc.returncode, cmd)
+            if os.path.exists(out + ".tmp"):
+                os.remove(out + ".tmp")
+        else:
+            os.replace(out + ".tmp", out)
+    if failed:
+        raise failed
 
 
 def gpu_units_lib():
@@ -49,6 +65,13 @@ def gpu_units_lib():
     if not os.path.exists(GU_LIB):
         raise RuntimeError("tests/native/libgpu_units.so not built (run __graft_entry__.build())")
     return ctypes.CDLL(GU_LIB)
+
+
+def gpu_units_pair_lib():
+    """ctypes handle on tests/native/libgpu_units_pair.so (built by __graft_entry__.build(); -m gpu tests only)."""
+    if not os.path.exists(GUP_LIB):
+        raise RuntimeError("tests/native/libgpu_units_pair.so not built (run __graft_entry__.build())")
+    return ctypes.CDLL(GUP_LIB)
 
 
 def build_cpu_baseline():
@@ -77,7 +100,8 @@ CT_LIB = os.path.join(HERE, "native", "libhost_ops_contract.so")
 
 
 def _contract_lib():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    deps = [SRC, os.path.join(HERE, "native", "arith_units.h")]
+    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     if not os.path.exists(CT_LIB) or any(os.path.getmtime(d) > os.path.getmtime(CT_LIB) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DBLS_CONTRACT_CHECK", "-o",
                                CT_LIB + ".tmp", SRC])

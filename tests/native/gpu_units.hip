@@ -11,10 +11,16 @@
 //   gu_quad             final_exponentiation_quad / fp12q_exp_xabs (lg2.h), a lane quad per element, the
 //                       value in full on all four lanes; each lane's result is returned, so the test sees that the four
 //                       agree.  Fp2 elements and the identity take the quad's degenerate branch (Granger-Scott).
+//   gu_fp_op, gu_fp2_op, gu_fp12_op, gu_curve_op, gu_h2c_op, gu_pairing_op
+//                       one dispatcher per arithmetic layer (arith_units.h: the ops and the record layouts), one case
+//                       per lane, for tests/test_gpu_arith_layers.py.  The host build runs the same dispatchers
+//                       (host_ops.cpp ht_arith) on the same cases (tests/arith_cases.py).
 // Elements cross the ABI as 12 big-endian 48-byte Fp coefficients (c0.c0.c0 .. c1.c2.c1), canonical, not Montgomery.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+
+#include "arith_units.h"
 
 using namespace bls;
 
@@ -118,9 +124,58 @@ int run(unsigned lanes, const uint8_t* in, uint8_t* out, uint64_t n, int extra_o
   return rc;
 }
 
+// One case per lane through a layer's dispatcher (arith_units.h); records are in_bytes / out_bytes apart.
+template <int LAYER>
+__global__ void __launch_bounds__(64) k_gu_arith(const uint8_t* in, uint8_t* out, uint64_t n, int op) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* a = in + au::in_bytes(LAYER) * i;
+  uint8_t* o = out + au::out_bytes(LAYER) * i;
+  if constexpr (LAYER == au::AU_FP)
+    au::fp_case(op, a, o);
+  else if constexpr (LAYER == au::AU_FP2)
+    au::fp2_case(op, a, o);
+  else if constexpr (LAYER == au::AU_FP12)
+    au::fp12_case(op, a, o);
+  else if constexpr (LAYER == au::AU_CURVE_G1)
+    au::curve_case<fp>(op, a, o);
+  else if constexpr (LAYER == au::AU_CURVE_G2)
+    au::curve_case<fp2>(op, a, o);
+  else if constexpr (LAYER == au::AU_H2C)
+    au::h2c_case(op, a, o);
+  else
+    au::pair_case(op, a, o);
+}
+
+template <int LAYER>
+int run_arith(int op, const uint8_t* in, uint8_t* out, uint64_t n) {
+  if (!n) return 0;
+  const size_t ib = au::in_bytes(LAYER) * n, ob = au::out_bytes(LAYER) * n;
+  uint8_t *din = nullptr, *dout = nullptr;
+  if (check(hipMalloc(&din, ib)) || check(hipMalloc(&dout, ob))) return 1;
+  int rc = check(hipMemcpy(din, in, ib, hipMemcpyHostToDevice)) || check(hipMemset(dout, 0, ob));
+  if (!rc) {
+    hipLaunchKernelGGL(k_gu_arith<LAYER>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, din, dout, n, op);
+    rc = check(hipGetLastError()) || check(hipDeviceSynchronize()) ||
+         check(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
+  }
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+int gu_fp_op(int op, const uint8_t* in, uint8_t* out, uint64_t n) { return run_arith<au::AU_FP>(op, in, out, n); }
+int gu_fp2_op(int op, const uint8_t* in, uint8_t* out, uint64_t n) { return run_arith<au::AU_FP2>(op, in, out, n); }
+int gu_fp12_op(int op, const uint8_t* in, uint8_t* out, uint64_t n) { return run_arith<au::AU_FP12>(op, in, out, n); }
+// g = 1: F = fp (G1); g = 2: F = fp2 (G2)
+int gu_curve_op(int g, int op, const uint8_t* in, uint8_t* out, uint64_t n) {
+  return g == 1 ? run_arith<au::AU_CURVE_G1>(op, in, out, n) : run_arith<au::AU_CURVE_G2>(op, in, out, n);
+}
+int gu_h2c_op(int op, const uint8_t* in, uint8_t* out, uint64_t n) { return run_arith<au::AU_H2C>(op, in, out, n); }
+int gu_pairing_op(int op, const uint8_t* in, uint8_t* out, uint64_t n) { return run_arith<au::AU_PAIR>(op, in, out, n); }
 int gu_final_exp(const uint8_t* in, uint8_t* out, uint64_t n) {
   return n ? run((unsigned)n, in, out, n, 0, false) : 0;
 }

@@ -677,3 +677,25 @@ extern "C" uint32_t ht_rlcb_set_g1_min(uint32_t min) {
   return o;
 }
 extern "C" uint64_t ht_rlcb_chunk_count(uint64_t n, uint64_t slots) { return rlcb_chunk_count(n, slots); }
+
+// ---- every arithmetic layer on fixed-size case records (arith_units.h), the host side of tests/arith_cases.py -----
+#include "arith_units.h"
+
+// n cases of one layer (au::AU_*) through op; the GPU library runs the same dispatchers one case per lane
+extern "C" int ht_arith(int layer, int op, const uint8_t* in, uint8_t* out, uint64_t n) {
+  if (layer < 0 || layer >= au::AU_LAYERS) return 2;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint8_t* a = in + (uint64_t)au::in_bytes(layer) * i;
+    uint8_t* o = out + (uint64_t)au::out_bytes(layer) * i;
+    switch (layer) {
+      case au::AU_FP: au::fp_case(op, a, o); break;
+      case au::AU_FP2: au::fp2_case(op, a, o); break;
+      case au::AU_FP12: au::fp12_case(op, a, o); break;
+      case au::AU_CURVE_G1: au::curve_case<fp>(op, a, o); break;
+      case au::AU_CURVE_G2: au::curve_case<fp2>(op, a, o); break;
+      case au::AU_H2C: au::h2c_case(op, a, o); break;
+      default: au::pair_case(op, a, o);
+    }
+  }
+  return 0;
+}

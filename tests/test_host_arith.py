@@ -1,8 +1,11 @@
 """Layer-by-layer parity of the kernel arithmetic (host build, tests/native) against the oracle.
 
 The kernels' per-lane code in charon_amd/csrc is compiled for x86 here, so every field/tower/curve/
-hash/pairing layer is diffed against oracle/bls12381.py on the CPU.  The GPU tests then only have to
-show the device build computes the same thing (tests/test_gpu_parity.py).
+hash/pairing layer is diffed against oracle/bls12381.py on the CPU.  This is the x86 build: the device
+build replaces the Fp / Fp2 products, the modular add / sub / neg and the inverse's divstep with asm routines
+and has a split-Fp2 variant, none of which runs here.  The device build's own layer tests are
+tests/test_gpu_arith_layers.py (case lists in tests/arith_cases.py, shared with tests/test_arith_cases_host.py);
+tests/test_gpu_parity.py then checks whole calls end to end.
 """
 import random
 
