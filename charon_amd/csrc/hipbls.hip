@@ -60,6 +60,16 @@ __global__ void k_rlcb_items(uint64_t n, const uint8_t* pks, const uint8_t* sigs
                              int32_t* status, const uint32_t* key_idx, uint64_t T, const int32_t* tcode,
                              const uint32_t* tab, const uint32_t* g1pos, uint32_t* gpts, uint32_t* gsc,
                              bls::keycache kc);
+// the same two stages publishing to the signature cache (sigcache.h), launched only with that cache on
+__global__ void k_rlc_items_sc(uint64_t i0, uint64_t i1, const uint8_t* pks, const uint8_t* sigs,
+                               const uint32_t* msg_idx, uint64_t n, uint64_t n_msgs, bls::rlc_seed seed, uint32_t* rpk,
+                               uint32_t* rsig, int32_t* status, const uint32_t* key_idx, uint64_t T,
+                               const int32_t* tcode, const uint32_t* tab, bls::keycache kc, bls::sigcache sc);
+__global__ void k_rlcb_items_sc(uint64_t n, const uint8_t* pks, const uint8_t* sigs, const uint32_t* msg_idx,
+                                uint64_t n_msgs, bls::rlc_seed seed, uint32_t* rpk, uint32_t* pts, uint32_t* sc,
+                                int32_t* status, const uint32_t* key_idx, uint64_t T, const int32_t* tcode,
+                                const uint32_t* tab, const uint32_t* g1pos, uint32_t* gpts, uint32_t* gsc,
+                                bls::keycache kc, bls::sigcache sgc);
 }
 
 // Secret-independent Sign and SecretToPublicKey (sign_ct.hip: its own translation unit, C linkage).
@@ -251,6 +261,35 @@ constexpr uint64_t kRootCacheDefaultSlots = 262144;  // x 256 B = 64 MiB (+ 1 Mi
 constexpr uint64_t kRootCacheMaxSlots = 1ull << 22;
 constexpr uint64_t kRootCacheMaxLines = 1ull << 22;  // x 19,712 B; the default is half the slots (2.4 GiB at 262,144)
 
+// Resident signature cache (sigcache.h): a signature's 96 wire bytes -> its decoded point, filled by
+// the Verify and RLC kernels (k_sigcache_insert, k_rlc_items_sc, k_rlcb_items_sc) and read by sigagg's scaling lanes
+// (k_tagg_scale_sc, k_tv_phase_a_sc, k_tv_phase_a_keys_sc).  Off (0 slots) unless hipbls_sigcache_config or
+// HIPBLS_SIGCACHE_SLOTS turns it on; off, every call launches the kernels it launched before the cache existed.
+// The host owns the buffers and the generations, as RootCache: `mu` is held across "copy the struct, enqueue the
+// kernel" and by config and the rollover from before they wait for the device until the buffers are zeroed.
+// Lock order: the context's mu (where held), RootCache::mu, KeyCache::mu, then this one.
+struct SigCache {
+  std::mutex mu;
+  uint64_t slots = 0;  // power of two; 0 = off
+  uint32_t* entries = nullptr;
+  uint32_t* claim = nullptr;
+  unsigned long long* ctr = nullptr;  // hits, misses, inserts (all since the last config)
+  // pinned: the device's insert counter as of the last producer kernel whose stream has reached the copy behind it
+  unsigned long long* h_ins = nullptr;
+  uint64_t gen_base = 0;   // the insert counter when this generation began
+  uint64_t rollovers = 0;  // generations ended since the last config
+  bls::sigcache dev() const {
+    bls::sigcache k{};
+    if (slots) {
+      k.entries = entries;
+      k.claim = claim;
+      k.ctr = ctr;
+      k.mask = (uint32_t)(slots - 1);
+    }
+    return k;
+  }
+};
+
 // One open or running batch of the submission queue.
 struct VBatch {
   std::vector<uint8_t> pk, sig, msg;
@@ -401,7 +440,8 @@ struct Context {
   HCache hcache;
   KeyCache kcache;
   RootCache rcache;
-  std::mutex tmu;                            // timing table (also used by the queue worker)
+  SigCache scache;
+  std::mutex tmu;                           // timing table (also used by the queue worker)
   std::map<std::string, TimingSlot> timing;  // per kernel name: HIP events on the launch stream
   VerifyQueue q;
 };
@@ -530,6 +570,54 @@ uint64_t rootcache_default_slots() {
   return (uint64_t)v;
 }
 
+// The signature cache's counterpart of rootcache_setup: `slots` slots (0: off; rounded up to a power of two, at least
+// a probe window), all empty, counters and generation state zero.  SigCache::mu is held, the context's device is
+// current and no kernel that takes the cache runs or can be enqueued.
+int sigcache_setup(SigCache& sc, uint64_t slots, hipStream_t s) {
+  if (slots > bls::SC_MAX_SLOTS) return arg_err("signature cache above 2^22 slots");
+  uint64_t want = 0;
+  if (slots) {
+    want = bls::KC_MIN_SLOTS;
+    while (want < slots) want <<= 1;
+  }
+  if (want != sc.slots) {
+    if (sc.entries) (void)hipFree(sc.entries);
+    if (sc.claim) (void)hipFree(sc.claim);
+    sc.entries = sc.claim = nullptr;
+    sc.slots = 0;
+    if (want) {
+      HIP_TRY(hipMalloc((void**)&sc.entries, want * bls::SC_WORDS * 4));
+      HIP_TRY(hipMalloc((void**)&sc.claim, want * 4));
+      sc.slots = want;
+    }
+  }
+  if (!want && !sc.ctr) return HIPBLS_OK;  // never turned on: nothing to allocate or zero
+  if (!sc.ctr) HIP_TRY(hipMalloc((void**)&sc.ctr, 3 * sizeof(unsigned long long)));
+  if (!sc.h_ins) HIP_TRY(hipHostMalloc((void**)&sc.h_ins, sizeof(unsigned long long), hipHostMallocDefault));
+  HIP_TRY(hipMemsetAsync(sc.ctr, 0, 3 * sizeof(unsigned long long), s));
+  if (sc.slots) {
+    HIP_TRY(hipMemsetAsync(sc.claim, 0, sc.slots * 4, s));
+    HIP_TRY(hipMemsetAsync(sc.entries, 0, sc.slots * bls::SC_WORDS * 4, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  *sc.h_ins = 0;
+  sc.gen_base = 0;
+  sc.rollovers = 0;
+  return HIPBLS_OK;
+}
+// HIPBLS_SIGCACHE_SLOTS sets the size; unset or 0: off.
+uint64_t sigcache_default_slots() {
+  const char* e = getenv("HIPBLS_SIGCACHE_SLOTS");
+  if (!e || !e[0]) return 0;
+  char* end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  if (end == e || *end || v > bls::SC_MAX_SLOTS) {
+    fprintf(stderr, "hipbls: HIPBLS_SIGCACHE_SLOTS=%s ignored (expected 0 .. 2^22)\n", e);
+    return 0;
+  }
+  return (uint64_t)v;
+}
+
 // HIPBLS_ROOTCACHE_LINES sets the line pool's block count; 0 turns the lines off.
 uint64_t rootcache_default_lines() {
   const char* e = getenv("HIPBLS_ROOTCACHE_LINES");
@@ -649,6 +737,8 @@ const KernelRef kKernels[] = {
     KREF(k_root_lookup),
     KREF(k_sign_ct_hash), KREF(k_sign_ct_mul), KREF(k_sk_to_pk_ct),
     KREF(k_g1_comb_build), KREF(k_deal_ct), KREF(k_recover_plan), KREF(k_recover_ct),
+    KREF(k_sigcache_insert), KREF(k_verify_prep_keys_sc), KREF(k_rlc_items_sc), KREF(k_rlcb_items_sc),
+    KREF(k_tagg_scale_sc), KREF(k_tv_phase_a_sc), KREF(k_tv_phase_a_keys_sc),
 };
 #define RES(s) reinterpret_cast<const void*>(&k_scratch_reserve<s>)
 // 8 KiB to the per-lane budget (charon_amd/codeobj.py PRIVATE_SEGMENT_BUDGET, 13,104 B) in 256-byte steps: at most
@@ -813,6 +903,8 @@ int init_locked(const std::vector<int>& ids) {
       c->rcache.lines_want = rootcache_default_lines();
       const int rrc = rootcache_setup(c->rcache, rootcache_default_slots(), c->stream);
       if (rrc) return rrc;
+      const int src = sigcache_setup(c->scache, sigcache_default_slots(), c->stream);
+      if (src) return src;
     }
     made.push_back(c);
   }
@@ -1334,6 +1426,75 @@ int launch_verify_fused(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs,
   return HIPBLS_OK;
 }
 
+// Signatures age, as roots do: a producer call ends the signature cache's generation before it launches if the
+// inserts a finished call last reported have reached half the slots (rootcache_roll_if_due's steps: both locks, a
+// wait for the device, the claims and entries zeroed on the library stream).  Only producers end a generation: a
+// consumer needs no free slot, and emptying the table in front of a sigagg call would only cost that call its hits.
+bool sigcache_due(const SigCache& S) {
+  return S.slots && bls::sc_generation_due(*(volatile unsigned long long*)S.h_ins, S.gen_base, S.slots);
+}
+int sigcache_roll_if_due(Context& c, bool ctx_locked) {
+  SigCache& S = c.scache;
+  {
+    std::lock_guard<std::mutex> g(S.mu);
+    if (!sigcache_due(S)) return HIPBLS_OK;
+  }
+  std::unique_lock<std::mutex> cl(c.mu, std::defer_lock);
+  if (!ctx_locked) cl.lock();
+  std::lock_guard<std::mutex> g(S.mu);
+  if (!sigcache_due(S)) return HIPBLS_OK;  // another caller ended the generation, or config replaced the table
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long ins = 0;
+  HIP_TRY(hipMemcpyAsync(&ins, S.ctr + 2, sizeof(ins), hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipMemsetAsync(S.claim, 0, S.slots * 4, c.stream));
+  HIP_TRY(hipMemsetAsync(S.entries, 0, S.slots * bls::SC_WORDS * 4, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  *S.h_ins = ins;
+  S.gen_base = ins;
+  S.rollovers += 1;
+  return HIPBLS_OK;
+}
+// Held across "copy the cache struct, enqueue the kernel" (SigCache::mu); taken after KeyCache::mu where both are.
+#define SC_LAUNCH_GUARD(c) std::lock_guard<std::mutex> _scl((c).scache.mu)
+// A producer's last step, under SC_LAUNCH_GUARD: the insert counter, for the next call's generation check -- a copy
+// behind the kernel on its stream, never waited for.
+int sigcache_note_inserts(Context& c, const bls::sigcache& scd, hipStream_t s) {
+  if (scd.entries)
+    HIP_TRY(hipMemcpyAsync(c.scache.h_ins, scd.ctr + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  return HIPBLS_OK;
+}
+
+// The signature cache's producer behind a prep + pair Verify (kernels.h k_sigcache_insert): d_pks, or the keys'
+// table indices.  Not launched with the cache off.
+int launch_sigcache_insert(Context& c, const uint8_t* d_pks, const uint32_t* d_kidx, const uint8_t* d_sigs, uint64_t n,
+                           const DevBuf& ws, const int32_t* d_status, hipStream_t s) {
+  SC_LAUNCH_GUARD(c);
+  const bls::sigcache scd = c.scache.dev();
+  if (!scd.entries) return HIPBLS_OK;
+  // the table only for the keyed call, which holds the context lock (the queue's worker runs the wire form without it)
+  const uint64_t T = d_pks ? 0 : c.t_size;
+  const int32_t* tcode = d_pks ? nullptr : (const int32_t*)c.t_code.p;
+  const int rc = timed(c, "sigcache_insert", s, [&] {
+    hipLaunchKernelGGL(k_sigcache_insert, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_pks, d_kidx, T, tcode,
+                       d_sigs, n, (const uint32_t*)ws.p, d_status, scd);
+  });
+  if (rc) return rc;
+  return sigcache_note_inserts(c, scd, s);
+}
+
+// The check behind a prep stage: lane quads or lane pairs on the prep's workspace.
+int launch_verify_pair(Context& c, const DevBuf& ws, uint64_t n, int32_t* d_status, hipStream_t s) {
+  if (use_quads(n))
+    return timed(c, "verify_pair_lq4", s, [&] {
+      hipLaunchKernelGGL(k_verify_pair_lq4, dim3((unsigned)grid_for(4 * n)), dim3(kBlock), 0, s,
+                         (const uint32_t*)ws.p, n, d_status);
+    });
+  return timed(c, "verify_pair_lg2", s, [&] {
+    hipLaunchKernelGGL(k_verify_pair_lg2, dim3((unsigned)grid_for(2 * n)), dim3(kBlock), 0, s,
+                       (const uint32_t*)ws.p, n, d_status);
+  });
+}
+
 // Verify: fused (one lane per item) or prep + lane-pair check; `ws` is the caller's workspace (the fused route's
 // order and slots; 120 words per item of SoA points for the latter), so the library stream and the queue worker never
 // share one.  ctx_locked: whether the caller holds the context's lock (rootcache_roll_if_due).
@@ -1354,6 +1515,8 @@ int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const
     if (rc) return rc;
     return launch_oct_check(c, ws, n, d_status, s, R);
   }
+  rc = sigcache_roll_if_due(c, ctx_locked);  // this route fills the signature cache (off: nothing is due)
+  if (rc) return rc;
   rc = timed(c, "verify_prep", s, [&] {
     const int pair_hash = n <= kPairHashMaxVerify ? 1 : 0;
     KC_LAUNCH_GUARD(c);
@@ -1361,15 +1524,9 @@ int launch_verify(Context& c, const uint8_t* d_pks, const uint8_t* d_msgs, const
                        d_msgs, d_offs, d_sigs, n, (uint32_t*)ws.p, d_status, pair_hash, c.kcache.dev());
   });
   if (rc) return rc;
-  if (use_quads(n))
-    return timed(c, "verify_pair_lq4", s, [&] {
-      hipLaunchKernelGGL(k_verify_pair_lq4, dim3((unsigned)grid_for(4 * n)), dim3(kBlock), 0, s,
-                         (const uint32_t*)ws.p, n, d_status);
-    });
-  return timed(c, "verify_pair_lg2", s, [&] {
-    hipLaunchKernelGGL(k_verify_pair_lg2, dim3((unsigned)grid_for(2 * n)), dim3(kBlock), 0, s,
-                       (const uint32_t*)ws.p, n, d_status);
-  });
+  rc = launch_verify_pair(c, ws, n, d_status, s);
+  if (rc) return rc;
+  return launch_sigcache_insert(c, d_pks, nullptr, d_sigs, n, ws, d_status, s);  // nothing with the cache off
 }
 
 bool use_rlc_batch(Context& c, uint64_t n);
@@ -1448,6 +1605,8 @@ int launch_rlc(Context& c, const uint8_t* d_pks, const uint8_t* d_sigs, const ui
   if (n > 0xffffffffull) return arg_err("RLC batch larger than 2^32 items");  // fallback list holds 32-bit indices
   int rc = ensure_rlc_streams(c);
   if (rc) return rc;
+  rc = sigcache_roll_if_due(c, true);  // the item stages fill the signature cache (off: nothing is due)
+  if (rc) return rc;
   const uint64_t n_win = (n + RLC_W - 1) / RLC_W;
   HIP_TRY(c.r_pk.ensure(n * 36 * 4));
   HIP_TRY(c.r_sig.ensure(n * 72 * 4));
@@ -1511,11 +1670,24 @@ int launch_rlc(Context& c, const uint8_t* d_pks, const uint8_t* d_sigs, const ui
     if (w0 >= w1) continue;
     const uint64_t i0 = w0 * RLC_W, i1 = w1 * RLC_W < n ? w1 * RLC_W : n;
     HIP_TRY(hipStreamWaitEvent(ss, c.ev_fork, 0));
-    rc = timed(c, "rlc_items", ss, [&] {
+    {
       KC_LAUNCH_GUARD(c);
-      hipLaunchKernelGGL(k_rlc_items, dim3((unsigned)grid_for(i1 - i0)), dim3(kBlock), 0, ss, i0, i1, d_pks, d_sigs,
-                         d_midx, n, n_msgs, seed, rpk, rsig, d_status, d_kidx, T, tcode, tab, c.kcache.dev());
-    });
+      SC_LAUNCH_GUARD(c);
+      const bls::sigcache scd = c.scache.dev();
+      if (scd.entries) {  // the kernel that also publishes the signatures it decoded (sigcache.h)
+        rc = timed(c, "rlc_items_sc", ss, [&] {
+          hipLaunchKernelGGL(k_rlc_items_sc, dim3((unsigned)grid_for(i1 - i0)), dim3(kBlock), 0, ss, i0, i1, d_pks,
+                             d_sigs, d_midx, n, n_msgs, seed, rpk, rsig, d_status, d_kidx, T, tcode, tab,
+                             c.kcache.dev(), scd);
+        });
+        if (!rc) rc = sigcache_note_inserts(c, scd, ss);
+      } else {
+        rc = timed(c, "rlc_items", ss, [&] {
+          hipLaunchKernelGGL(k_rlc_items, dim3((unsigned)grid_for(i1 - i0)), dim3(kBlock), 0, ss, i0, i1, d_pks, d_sigs,
+                             d_midx, n, n_msgs, seed, rpk, rsig, d_status, d_kidx, T, tcode, tab, c.kcache.dev());
+        });
+      }
+    }
     if (rc) return rc;
     HIP_TRY(hipStreamWaitEvent(ss, c.ev_hash, 0));
     if (use_pairs(w1 - w0, kLg2MaxWindows))
@@ -1723,12 +1895,25 @@ int launch_rlc_batch(Context& c, const uint8_t* d_pks, const uint8_t* d_sigs, co
     });
     if (rc) return rc;
   }
-  rc = timed(c, "rlcb_items", s0, [&] {
+  {
     KC_LAUNCH_GUARD(c);
-    hipLaunchKernelGGL(k_rlcb_items, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s0, n, d_pks, d_sigs, d_midx, n_msgs,
-                       seed, rpk, pts, sc, d_status, d_kidx, T, tcode, tab, (const uint32_t*)G(gl.pos), G(gl.pts),
-                       G(gl.sc), c.kcache.dev());
-  });
+    SC_LAUNCH_GUARD(c);
+    const bls::sigcache scd = c.scache.dev();
+    if (scd.entries) {  // the kernel that also publishes the signatures it decoded (sigcache.h)
+      rc = timed(c, "rlcb_items_sc", s0, [&] {
+        hipLaunchKernelGGL(k_rlcb_items_sc, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s0, n, d_pks, d_sigs, d_midx,
+                           n_msgs, seed, rpk, pts, sc, d_status, d_kidx, T, tcode, tab, (const uint32_t*)G(gl.pos),
+                           G(gl.pts), G(gl.sc), c.kcache.dev(), scd);
+      });
+      if (!rc) rc = sigcache_note_inserts(c, scd, s0);
+    } else {
+      rc = timed(c, "rlcb_items", s0, [&] {
+        hipLaunchKernelGGL(k_rlcb_items, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s0, n, d_pks, d_sigs, d_midx,
+                           n_msgs, seed, rpk, pts, sc, d_status, d_kidx, T, tcode, tab, (const uint32_t*)G(gl.pos),
+                           G(gl.pts), G(gl.sc), c.kcache.dev());
+      });
+    }
+  }
   if (rc) return rc;
   HIP_TRY(hipEventRecord(c.rlcb_ev_items, s0));
   rc = timed(c, "rlcb_msm", s0, [&] {
@@ -1880,6 +2065,23 @@ bool use_tagg_lat(uint64_t n_groups, uint64_t n_parts) {
          n_parts <= kTaggLatMaxParts;
 }
 
+// sigagg's scaling stage as a launch of its own: k_tagg_scale, or with the signature cache on the kernel that looks
+// the partials up first (sigcache.h; lookups only).
+int launch_tagg_scale(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const uint64_t* d_goffs,
+                      uint64_t n_groups, uint64_t n_parts, uint32_t* pts, int32_t* pst, hipStream_t s) {
+  SC_LAUNCH_GUARD(c);
+  const bls::sigcache scd = c.scache.dev();
+  if (scd.entries)
+    return timed(c, "tagg_scale_sc", s, [&] {
+      hipLaunchKernelGGL(k_tagg_scale_sc, dim3((unsigned)grid_for(n_parts)), dim3(kBlock), 0, s, d_sigs, d_ids, d_goffs,
+                         n_groups, n_parts, pts, pst, scd);
+    });
+  return timed(c, "tagg_scale", s, [&] {
+    hipLaunchKernelGGL(k_tagg_scale, dim3((unsigned)grid_for(n_parts)), dim3(kBlock), 0, s, d_sigs, d_ids, d_goffs,
+                       n_groups, n_parts, pts, pst);
+  });
+}
+
 int launch_tagg(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const uint64_t* d_goffs, uint64_t n_groups,
                 uint64_t n_parts, uint8_t* d_out, int32_t* d_status, hipStream_t s) {
   if (n_groups == 0) return HIPBLS_OK;
@@ -1906,10 +2108,7 @@ int launch_tagg(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, const u
     return ws_end(c, s);
   }
   if (n_parts) {
-    rc = timed(c, "tagg_scale", s, [&] {
-      hipLaunchKernelGGL(k_tagg_scale, dim3((unsigned)grid_for(n_parts)), dim3(kBlock), 0, s, d_sigs, d_ids, d_goffs,
-                         n_groups, n_parts, (uint32_t*)c.b_pts.p, (int32_t*)c.b_pst.p);
-    });
+    rc = launch_tagg_scale(c, d_sigs, d_ids, d_goffs, n_groups, n_parts, (uint32_t*)c.b_pts.p, (int32_t*)c.b_pst.p, s);
     if (rc) return rc;
   }
   rc = timed(c, "tagg_sum", s, [&] {
@@ -2038,28 +2237,41 @@ int launch_tagg_verify(Context& c, const uint8_t* d_sigs, const int64_t* d_ids, 
     // one launch whatever the group count: the hash role covers the miss list only, always on lane pairs
     const uint64_t nprep = grid_for(n_groups) + (K->n_hash ? grid_for(2 * K->n_hash) : 0),
                    nscale = n_parts ? grid_for(n_parts) : 0;
-    rc = timed(c, "tv_phase_a_keys", s, [&] {
-      hipLaunchKernelGGL(k_tv_phase_a_keys, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, K->d_kidx, T, tcode,
-                         tab, d_msgs, d_moffs, K->d_mlist, K->n_hash, K->n_msgs, Hc, n_groups, d_ids, d_goffs, ws,
-                         d_vstatus, d_sigs, n_parts, pts, pst);
-    });
+    SC_LAUNCH_GUARD(c);
+    const bls::sigcache scd = c.scache.dev();
+    if (scd.entries)  // the scaling role looks its partials up in the signature cache (sigcache.h)
+      rc = timed(c, "tv_phase_a_keys_sc", s, [&] {
+        hipLaunchKernelGGL(k_tv_phase_a_keys_sc, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, K->d_kidx, T,
+                           tcode, tab, d_msgs, d_moffs, K->d_mlist, K->n_hash, K->n_msgs, Hc, n_groups, d_ids, d_goffs,
+                           ws, d_vstatus, d_sigs, n_parts, pts, pst, scd);
+      });
+    else
+      rc = timed(c, "tv_phase_a_keys", s, [&] {
+        hipLaunchKernelGGL(k_tv_phase_a_keys, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, K->d_kidx, T, tcode,
+                           tab, d_msgs, d_moffs, K->d_mlist, K->n_hash, K->n_msgs, Hc, n_groups, d_ids, d_goffs, ws,
+                           d_vstatus, d_sigs, n_parts, pts, pst);
+      });
   } else if (BLS_TV_PAIR_HASH && n_groups <= kPairHashMaxVerify) {
     const uint64_t nprep = 3 * grid_for(n_groups), nscale = n_parts ? grid_for(n_parts) : 0;
-    rc = timed(c, "tv_phase_a", s, [&] {
-      hipLaunchKernelGGL(k_tv_phase_a, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, d_dvpks, d_msgs, d_moffs,
-                         n_groups, d_ids, d_goffs, ws, d_vstatus, d_sigs, n_parts, pts, pst);
-    });
+    SC_LAUNCH_GUARD(c);
+    const bls::sigcache scd = c.scache.dev();
+    if (scd.entries)
+      rc = timed(c, "tv_phase_a_sc", s, [&] {
+        hipLaunchKernelGGL(k_tv_phase_a_sc, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, d_dvpks, d_msgs,
+                           d_moffs, n_groups, d_ids, d_goffs, ws, d_vstatus, d_sigs, n_parts, pts, pst, scd);
+      });
+    else
+      rc = timed(c, "tv_phase_a", s, [&] {
+        hipLaunchKernelGGL(k_tv_phase_a, dim3((unsigned)(nprep + nscale)), dim3(kBlock), 0, s, d_dvpks, d_msgs, d_moffs,
+                           n_groups, d_ids, d_goffs, ws, d_vstatus, d_sigs, n_parts, pts, pst);
+      });
   } else {
     rc = timed(c, "tv_prep_pk", s, [&] {
       hipLaunchKernelGGL(k_tv_prep_pk, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, d_dvpks, d_msgs,
                          d_moffs, n_groups, d_ids, d_goffs, ws, d_vstatus);
     });
     if (rc) return rc;
-    if (n_parts)
-      rc = timed(c, "tagg_scale", s, [&] {
-        hipLaunchKernelGGL(k_tagg_scale, dim3((unsigned)grid_for(n_parts)), dim3(kBlock), 0, s, d_sigs, d_ids,
-                           d_goffs, n_groups, n_parts, pts, pst);
-      });
+    if (n_parts) rc = launch_tagg_scale(c, d_sigs, d_ids, d_goffs, n_groups, n_parts, pts, pst, s);
   }
   if (rc) return rc;
   rc = timed(c, "tagg_sum", s, [&] {
@@ -3461,6 +3673,39 @@ int verify_keys_host(Context& c, const uint32_t* key_idx, const uint8_t* msgs, c
   HIP_TRY(hipMemcpyAsync(c.b_sig.p, sigs, n * 96, hipMemcpyHostToDevice, c.stream));
   if (msg_total) HIP_TRY(hipMemcpyAsync(c.b_msg.p, msgs, msg_total, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipMemcpyAsync(c.b_off.p, offs, (n + 1) * 8, hipMemcpyHostToDevice, c.stream));
+  bool sc_on = false;
+  if (use_pairs(n, kLg2MaxVerify)) {
+    std::lock_guard<std::mutex> g(c.scache.mu);
+    sc_on = c.scache.slots != 0;
+  }
+  if (sc_on) {
+    // With the signature cache on, a batch the wire call would give to prep + pair takes the keyed twin of that route
+    // (kernels.h k_verify_prep_keys_sc, the same check, then the producer): k_verify_keys decodes and checks inside
+    // one lane and leaves no affine signature to publish.  Same statuses.
+    int rc = sigcache_roll_if_due(c, true);
+    if (rc) return rc;
+    rc = ws_begin(c, c.stream);
+    if (rc) return rc;
+    rc = verify_ws_ensure(c.v_ws, n, c.stream);
+    if (rc) return rc;
+    rc = timed(c, "verify_prep_keys_sc", c.stream, [&] {
+      hipLaunchKernelGGL(k_verify_prep_keys_sc, dim3((unsigned)(3 * grid_for(n))), dim3(kBlock), 0, c.stream,
+                         (const uint32_t*)c.b_kidx.p, c.t_size, (const int32_t*)c.t_code.p, (const uint32_t*)c.t_tab.p,
+                         (const uint8_t*)c.b_msg.p, (const uint64_t*)c.b_off.p, (const uint8_t*)c.b_sig.p, n,
+                         (uint32_t*)c.v_ws.p, (int32_t*)c.b_st.p);
+    });
+    if (rc) return rc;
+    rc = launch_verify_pair(c, c.v_ws, n, (int32_t*)c.b_st.p, c.stream);
+    if (rc) return rc;
+    rc = launch_sigcache_insert(c, nullptr, (const uint32_t*)c.b_kidx.p, (const uint8_t*)c.b_sig.p, n, c.v_ws,
+                                (const int32_t*)c.b_st.p, c.stream);
+    if (rc) return rc;
+    rc = ws_end(c, c.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HIPBLS_OK;
+  }
   int rc = timed(c, "verify_keys", c.stream, [&] {
     hipLaunchKernelGGL(k_verify_keys, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, c.stream,
                        (const uint32_t*)c.b_kidx.p, c.t_size, (const int32_t*)c.t_code.p, (const uint32_t*)c.t_tab.p,
@@ -4422,6 +4667,40 @@ int hipbls_rootcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, 
     *misses += v[1];
     *inserts += v[2];
     *rollovers += c.rcache.rollovers;
+  }
+  return HIPBLS_OK;
+}
+
+int hipbls_sigcache_config(uint64_t slots) {
+  if (slots > bls::SC_MAX_SLOTS) return arg_err("signature cache above 2^22 slots");
+  ENSURE_INIT();
+  return run_all([&](Context& c) -> int {
+    // as hipbls_rootcache_config: the context lock (run_all), then the cache's own, held from before the device wait
+    // until the new buffers stand
+    std::lock_guard<std::mutex> g(c.scache.mu);
+    HIP_TRY(hipDeviceSynchronize());
+    return sigcache_setup(c.scache, slots, c.stream);
+  });
+}
+
+int hipbls_sigcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, uint64_t* rollovers) {
+  if (!hits || !misses || !inserts || !rollovers) return arg_err("null output");
+  *hits = *misses = *inserts = *rollovers = 0;
+  ENSURE_INIT();
+  const int n = nctx();
+  for (int k = 0; k < n; ++k) {
+    Context& c = ctx(k);
+    ENTER_CTX(c);
+    std::lock_guard<std::mutex> g(c.scache.mu);
+    if (!c.scache.ctr) continue;
+    unsigned long long v[3] = {0, 0, 0};
+    HIP_TRY(hipDeviceSynchronize());  // the counters of every call that has been enqueued
+    HIP_TRY(hipMemcpyAsync(v, c.scache.ctr, sizeof(v), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    *hits += v[0];
+    *misses += v[1];
+    *inserts += v[2];
+    *rollovers += c.scache.rollovers;
   }
   return HIPBLS_OK;
 }

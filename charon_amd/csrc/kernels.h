@@ -308,6 +308,139 @@ k_tagg_scale(const uint8_t* __restrict__ sigs, const int64_t* __restrict__ ids, 
   tagg_scale_lane(blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n_groups, n_parts, pts, pstat);
 }
 
+// tagg_scale_lane for a call with the signature cache on (sigcache.h): the partial is looked up before
+// it is decoded (rlc.h tagg_scale_partial_sc: a hit skips the square root and the subgroup test; a miss is
+// tagg_scale_lane's code).  The id checks and the status precedence are tagg_scale_lane's.  Lookups only: sigagg
+// never fills the cache.  A lane function and kernels of their own: with the cache off a call runs the kernels above,
+// as it did before there was a signature cache.
+__device__ __forceinline__ void tagg_scale_lane_sc(uint64_t k, const uint8_t* __restrict__ sigs,
+                                                   const int64_t* __restrict__ ids, const uint64_t* __restrict__ goffs,
+                                                   uint64_t n_groups, uint64_t n_parts, uint32_t* __restrict__ pts,
+                                                   int32_t* __restrict__ pstat, const sigcache& sc) {
+  if (k >= n_parts) return;
+  uint64_t lo = 0, hi = n_groups;  // find g with goffs[g] <= k < goffs[g+1]
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) / 2;
+    if (goffs[mid] <= k)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const uint64_t g0 = goffs[lo], g1 = goffs[lo + 1];
+  const int t = (int)(g1 - g0);
+  const int me = (int)(k - g0);
+  int st = HIPBLS_OK;
+  for (int a = 0; a < t; ++a) {
+    if (ids[g0 + a] == 0) st = HIPBLS_ERR_COMBINE;
+    for (int b = a + 1; b < t; ++b)
+      if (ids[g0 + a] == ids[g0 + b]) st = HIPBLS_ERR_COMBINE;
+  }
+  g2j acc;
+  const int ds = tagg_scale_partial_sc(acc, sigs + 96 * k, ids + g0, t, me, st, sc);
+  if (ds == DEC_BAD) st = HIPBLS_ERR_SIGNATURE;
+  const uint32_t* src = &acc.x.c0.v[0];
+  for (int w = 0; w < 72; ++w) pts[(uint64_t)w * n_parts + k] = src[w];
+  pstat[k] = st;
+}
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLS_TAGG_WAVES, BLS_TAGG_WAVES)))
+k_tagg_scale_sc(const uint8_t* __restrict__ sigs, const int64_t* __restrict__ ids, const uint64_t* __restrict__ goffs,
+                uint64_t n_groups, uint64_t n_parts, uint32_t* __restrict__ pts, int32_t* __restrict__ pstat,
+                sigcache sc) {
+  tagg_scale_lane_sc(blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n_groups, n_parts, pts, pstat,
+                     sc);
+}
+
+// The signature cache's producer behind the prep + pair Verify routes (k_verify_prep, or its keyed twin below, then
+// k_verify_pair_lg2 / k_verify_pair_lq4), one lane per item, after the pair kernel: the affine signature lies in
+// ws + 72 n and the status is final.  Item i is published only if the prep stored a signature for it and its final
+// status is HIPBLS_OK or HIPBLS_ERR_VERIFY: then the pair's Miller loop proved the point to lie in G2 (a point outside
+// G2 is ERR_SIGNATURE).  "The prep stored it" is read off without a flag of its own: a prep that did not leave the
+// item pending set ERR_PUBKEY, ERR_SIGNATURE, or the status of an infinity key or signature, and DEC_INF needs the
+// infinity flag in the wire bytes (a key from the table: its code).  So a final OK / ERR_VERIFY with neither infinity
+// flag set means pending after the prep, and the words in ws are this item's.  The lane still compares x from the
+// wire bytes with the stored x before it publishes.  Inserts only: never reads an entry.
+__global__ void __launch_bounds__(kBlock) k_sigcache_insert(const uint8_t* __restrict__ pks,
+                                                            const uint32_t* __restrict__ key_idx, uint64_t T,
+                                                            const int32_t* __restrict__ tcode,
+                                                            const uint8_t* __restrict__ sigs, uint64_t n,
+                                                            const uint32_t* __restrict__ ws,
+                                                            const int32_t* __restrict__ status, sigcache sc) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int st = status[i];
+  if (st != HIPBLS_OK && st != HIPBLS_ERR_VERIFY) return;
+  const uint8_t* sig96 = sigs + 96 * i;
+  if ((sig96[0] & 0xc0) != 0x80) return;  // compressed, not infinity
+  if (pks) {
+    if (pks[48 * i] & 0x40) return;
+  } else {
+    const uint32_t k = key_idx[i];
+    if (k >= T || tcode[k] != DEC_OK) return;
+  }
+  g2a sig;
+  soa_load<48>(&sig.x.c0.v[0], ws + 72 * n, n, i);
+  fp2 x;
+  g2_x_from_wire(x, sig96);
+  if (!fp2_eq(x, sig.x)) return;
+  sig_publish(sc, sig96, sig);
+}
+
+// k_verify_prep's keyed twin (hipbls_verify_batch_keys with the signature cache on and a lane-pair or quad check):
+// the first grid_for(n) blocks take the keys from the resident table and decode the signatures, the next
+// 2 grid_for(n) hash the messages on lane pairs; same workspace, same statuses as k_verify_keys gives (key index out
+// of range: ERR_ARG).  The check is k_verify_pair_lg2 / k_verify_pair_lq4, the producer k_sigcache_insert.
+__global__ void __launch_bounds__(kBlock) k_verify_prep_keys_sc(const uint32_t* __restrict__ key_idx, uint64_t T,
+                                                                const int32_t* __restrict__ tcode,
+                                                                const uint32_t* __restrict__ tab,
+                                                                const uint8_t* __restrict__ msgs,
+                                                                const uint64_t* __restrict__ offs,
+                                                                const uint8_t* __restrict__ sigs, uint64_t n,
+                                                                uint32_t* __restrict__ ws,
+                                                                int32_t* __restrict__ status) {
+  const uint64_t nb = (n + kBlock - 1) / kBlock;
+  if (blockIdx.x >= nb) {  // uniform per workgroup
+    const uint64_t t = (blockIdx.x - nb) * (uint64_t)blockDim.x + threadIdx.x;
+    const uint64_t i = t >> 1;
+    if (i >= n) return;  // same on both lanes of the pair
+    const uint32_t m = (t & 1) ? ~0u : 0u;
+    const uint64_t o0 = offs[i], o1 = offs[i + 1];
+    g2j hj;
+    hash_to_g2_pair(hj, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, m);
+    if (!m) {
+      g2a hm;
+      jac_to_aff(hm, hj);
+      soa_store<48>(ws + 24 * n, n, i, &hm.x.c0.v[0]);
+    }
+    return;
+  }
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t k = key_idx[i];
+  if (k >= T) {
+    status[i] = HIPBLS_ERR_ARG;
+    return;
+  }
+  g1a pk;
+  g1j xpk;
+  g2a sig;
+  int st = RLC_PENDING;
+  const int dp = pubtab_get(pk, xpk, k, T, tcode, tab);
+  if (dp == DEC_BAD) {
+    st = HIPBLS_ERR_PUBKEY;
+  } else {
+    const int ds = g2_decompress(sig, sigs + 96 * i, false);  // G2 membership: from the pair's Miller loop
+    if (ds == DEC_BAD)
+      st = HIPBLS_ERR_SIGNATURE;
+    else if (dp == DEC_INF || ds == DEC_INF)
+      st = verify_inf_status(ds, sig);
+  }
+  if (st == RLC_PENDING) {
+    soa_store<24>(ws, n, i, &pk.x.v[0]);
+    soa_store<48>(ws + 72 * n, n, i, &sig.x.c0.v[0]);
+  }
+  status[i] = st;
+}
+
 // ThresholdAggregate, stage 2: one lane per group sums its scaled partials, multiplies the sum by L^-1 on the
 // small-integer path (ops.h lagrange_small), and compresses.
 __global__ void __launch_bounds__(kBlock) k_tagg_sum(const uint32_t* __restrict__ pts,
@@ -522,6 +655,20 @@ k_tv_phase_a(const uint8_t* __restrict__ pks, const uint8_t* __restrict__ msgs, 
   tagg_scale_lane((blockIdx.x - nprep) * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n, n_parts, pts,
                   pstat);
 }
+// k_tv_phase_a for a call with the signature cache on: the scaling role looks its partials up (tagg_scale_lane_sc).
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLS_TAGG_WAVES, BLS_TAGG_WAVES)))
+k_tv_phase_a_sc(const uint8_t* __restrict__ pks, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs,
+                uint64_t n, const int64_t* __restrict__ ids, const uint64_t* __restrict__ goffs,
+                uint32_t* __restrict__ ws, int32_t* __restrict__ vstatus, const uint8_t* __restrict__ sigs,
+                uint64_t n_parts, uint32_t* __restrict__ pts, int32_t* __restrict__ pstat, sigcache sc) {
+  const uint64_t nprep = 3 * ((n + kBlock - 1) / kBlock);
+  if (blockIdx.x < nprep) {
+    tv_prep_pk2_block(blockIdx.x, pks, msgs, offs, n, ids, goffs, ws, vstatus);
+    return;
+  }
+  tagg_scale_lane_sc((blockIdx.x - nprep) * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n, n_parts, pts,
+                     pstat, sc);
+}
 
 // Join: a group whose aggregation failed reports that status for its Verify too; otherwise the key's status
 // stands (Verify checks the key first), and an aggregate at infinity is "signature not verified".
@@ -590,6 +737,46 @@ k_tv_phase_a_keys(const uint32_t* __restrict__ key_idx, uint64_t T, const int32_
   }
   tagg_scale_lane((blockIdx.x - nkey - nhash) * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n, n_parts, pts,
                   pstat);
+}
+// k_tv_phase_a_keys for a call with the signature cache on: the key and hash roles are k_tv_phase_a_keys's (that
+// kernel stays as it is, so its roles are restated here), the scaling role looks its partials up.
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLS_TAGG_WAVES, BLS_TAGG_WAVES)))
+k_tv_phase_a_keys_sc(const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+                     const uint32_t* __restrict__ tab, const uint8_t* __restrict__ msgs,
+                     const uint64_t* __restrict__ offs, const uint32_t* __restrict__ mlist, uint64_t n_hash,
+                     uint64_t n_msgs, uint32_t* __restrict__ Hc, uint64_t n, const int64_t* __restrict__ ids,
+                     const uint64_t* __restrict__ goffs, uint32_t* __restrict__ ws, int32_t* __restrict__ vstatus,
+                     const uint8_t* __restrict__ sigs, uint64_t n_parts, uint32_t* __restrict__ pts,
+                     int32_t* __restrict__ pstat, sigcache sc) {
+  const uint64_t nkey = (n + kBlock - 1) / kBlock, nhash = (2 * n_hash + kBlock - 1) / kBlock;
+  if (blockIdx.x < nkey) {
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t g0 = goffs[i], g1 = goffs[i + 1];
+    g1a pk;
+    const int st = tv_key_lane(pk, key_idx[i], T, tcode, tab, ids + g0, (int)(g1 - g0));
+    if (st == RLC_PENDING) soa_store<24>(ws, n, i, &pk.x.v[0]);
+    vstatus[i] = st;
+    return;
+  }
+  if (blockIdx.x < nkey + nhash) {
+    const uint64_t t = (blockIdx.x - nkey) * (uint64_t)blockDim.x + threadIdx.x;
+    const uint64_t j = t >> 1;
+    if (j >= n_hash) return;  // same on both lanes of the pair
+    const uint32_t mask = (t & 1) ? ~0u : 0u;
+    const uint64_t m = mlist ? mlist[j] : j;
+    const uint64_t o0 = offs[m], o1 = offs[m + 1];
+    g2j hj;
+    hash_to_g2_pair(hj, msgs + o0, (uint32_t)(o1 - o0), DST_POP, 43, mask);
+    if (!mask) {
+      g2a hm;
+      jac_to_aff(hm, hj);
+      soa_store<48>(Hc, n_msgs, m, &hm.x.c0.v[0]);
+    }
+    return;
+  }
+  tagg_scale_lane_sc((blockIdx.x - nkey - nhash) * (uint64_t)blockDim.x + threadIdx.x, sigs, ids, goffs, n, n_parts,
+                     pts, pstat, sc);
 }
 
 // k_tv_join with the gather: group i's H(m) goes from its table (cache column or the call's own) into ws, the last

@@ -18,6 +18,7 @@
 #pragma once
 #include "keycache.h"
 #include "rootcache.h"
+#include "sigcache.h"
 #include "ops.h"
 
 namespace bls {
@@ -190,13 +191,82 @@ BLS_HD BLS_CALL int g1_decode_kc_pk(g1a& out, const uint8_t* b, const keycache& 
   return g1_decode_kc_body<false>(out, xP, b, kc);
 }
 
+// ---- the signature cache (sigcache.h) --------------------------------------------------------
+// x of a compressed G2 point from its wire bytes, as g2_decompress reads it (the caller knows the bytes decode DEC_OK).
+BLS_HD BLS_INLINE void g2_x_from_wire(fp2& x, const uint8_t* b96) {
+  uint8_t buf[96];
+  for (int i = 0; i < 96; ++i) buf[i] = b96[i];
+  buf[0] &= 0x1f;
+  fp_plain_from_be48(x.c1, buf);
+  fp_plain_from_be48(x.c0, buf + 48);
+  fp_to_mont(x.c0, x.c0);
+  fp_to_mont(x.c1, x.c1);
+}
+// A producer's step: `sig` is what sig96 decoded to, DEC_OK, and it is proven to lie in G2.
+BLS_HD BLS_CALL void sig_publish(const sigcache& sc, const uint8_t* sig96, const g2a& sig) {
+  uint32_t tag[24];
+  sc_tag_from_wire(tag, sig96);
+  sc_count(sc, 2, sc_insert(sc, tag, &sig.y.c0.v[0]));
+}
+
+// sigagg's scaling of one partial (kernels.h tagg_scale_lane's arithmetic) behind the signature cache: ids[0..t) are
+// the group's, me this partial's place, st the id checks' verdict.  A hit takes y from the entry and x from the wire
+// bytes: no square root, no subgroup test, and on the small-integer path [c_k] sig by a plain multiplication over
+// |c_k|'s bits instead of the subgroup test's 64-step chain.  A miss (or sc off) runs tagg_scale_lane's code.  The
+// Jacobian words of acc may differ between the two, the group element does not.  Returns the partial's DEC_* code.
+BLS_HD BLS_INLINE int tagg_scale_partial_sc(g2j& acc, const uint8_t* sig96, const int64_t* ids, int t, int me, int st,
+                                            const sigcache& sc) {
+  jac_set_inf(acc);
+  g2a s;
+  int64_t c;
+  uint64_t L;
+  const bool small = st == HIPBLS_OK && lagrange_small(ids, t, me, c, L);
+  bool hit = false;
+  if (sc.entries) {
+    uint32_t tag[24];
+    sc_tag_from_wire(tag, sig96);
+    hit = sc_lookup(sc, tag, &s.y.c0.v[0]);
+    sc_count(sc, 0, hit);
+    sc_count(sc, 1, !hit);
+  }
+  int ds;
+  if (hit) {
+    g2_x_from_wire(s.x, sig96);
+    ds = DEC_OK;
+    if (small) {
+      g2j sj;
+      jac_from_aff(sj, s);
+      g2_mul_i64(acc, sj, c);
+    }
+  } else {
+    ds = g2_decompress(s, sig96, !small);
+    if (small && ds == DEC_OK) {
+      g2j sj;
+      jac_from_aff(sj, s);
+      if (!g2_subgroup_and_mul_i64(acc, sj, c)) {
+        ds = DEC_BAD;
+        jac_set_inf(acc);
+      }
+    }
+  }
+  if (st == HIPBLS_OK && ds == DEC_OK && !small) {
+    g2j sj;
+    jac_from_aff(sj, s);
+    tagg_scale_point(acc, sj, ids, t, me);  // lambda_k sig_k (field path)
+  }
+  return ds;
+}
+
 // Stage 1 with the public key already decoded: dp = its DEC_* code, pk affine, xpk = [x] pk (from
 // g1_decompress_keep_x, either just now or once at load time in the resident pubshare table).
 // Decodes + subgroup-checks the signature in herumi's order, then stores [r_i] pk_i (G1 Jacobian,
 // 36 words) and [r_i] sig_i (G2 Jacobian, 72 words).  Items that already have their final status
 // (bad encoding, infinity) store the point at infinity.
-BLS_HD BLS_CALL int rlc_item_decoded(int dp, const g1a& pk, const g1j& xpk, const uint8_t* sig96, const rlc_seed& seed,
-                                     uint64_t i, uint32_t* rpk36, uint32_t* rsig72) {
+// SC: the lane publishes a signature that decoded DEC_OK (subgroup test included) to the signature cache.
+template <bool SC>
+BLS_HD BLS_INLINE int rlc_item_decoded_body(int dp, const g1a& pk, const g1j& xpk, const uint8_t* sig96,
+                                            const rlc_seed& seed, uint64_t i, uint32_t* rpk36, uint32_t* rsig72,
+                                            const sigcache& sc) {
   g1j rp;
   g2j rs;
   jac_set_inf(rp);
@@ -206,6 +276,9 @@ BLS_HD BLS_CALL int rlc_item_decoded(int dp, const g1a& pk, const g1j& xpk, cons
   g2a sig;
   if (st == RLC_PENDING) {
     const int ds = g2_decompress(sig, sig96, true);
+    if constexpr (SC) {
+      if (ds == DEC_OK) sig_publish(sc, sig96, sig);
+    }
     if (ds == DEC_BAD)
       st = HIPBLS_ERR_SIGNATURE;
     else if (dp == DEC_INF || ds == DEC_INF)
@@ -231,6 +304,15 @@ BLS_HD BLS_CALL int rlc_item_decoded(int dp, const g1a& pk, const g1j& xpk, cons
   for (int k = 0; k < 72; ++k) rsig72[k] = s[k];
   return st;
 }
+BLS_HD BLS_CALL int rlc_item_decoded(int dp, const g1a& pk, const g1j& xpk, const uint8_t* sig96, const rlc_seed& seed,
+                                     uint64_t i, uint32_t* rpk36, uint32_t* rsig72) {
+  return rlc_item_decoded_body<false>(dp, pk, xpk, sig96, seed, i, rpk36, rsig72, sigcache{});
+}
+BLS_HD BLS_CALL int rlc_item_decoded_sc(int dp, const g1a& pk, const g1j& xpk, const uint8_t* sig96,
+                                        const rlc_seed& seed, uint64_t i, uint32_t* rpk36, uint32_t* rsig72,
+                                        const sigcache& sc) {
+  return rlc_item_decoded_body<true>(dp, pk, xpk, sig96, seed, i, rpk36, rsig72, sc);
+}
 
 // Stage 1, one lane per item, from the wire-format public key.
 BLS_HD BLS_CALL int rlc_item(const uint8_t* pk48, const uint8_t* sig96, const rlc_seed& seed, uint64_t i,
@@ -246,6 +328,13 @@ BLS_HD BLS_CALL int rlc_item_kc(const uint8_t* pk48, const uint8_t* sig96, const
   g1j xpk;
   const int dp = g1_decode_kc_x(pk, xpk, pk48, kc);
   return rlc_item_decoded(dp, pk, xpk, sig96, seed, i, rpk36, rsig72);
+}
+BLS_HD BLS_CALL int rlc_item_kc_sc(const uint8_t* pk48, const uint8_t* sig96, const rlc_seed& seed, uint64_t i,
+                                   uint32_t* rpk36, uint32_t* rsig72, const keycache& kc, const sigcache& sc) {
+  g1a pk;
+  g1j xpk;
+  const int dp = g1_decode_kc_x(pk, xpk, pk48, kc);
+  return rlc_item_decoded_sc(dp, pk, xpk, sig96, seed, i, rpk36, rsig72, sc);
 }
 
 // ---- resident pubshare table: every pubshare decoded + subgroup-checked once ----
@@ -513,11 +602,13 @@ BLS_HD BLS_INLINE bool rlc_window(const f12l<LS>& F, uint64_t i0, uint64_t i1, c
 
 // Stage 1, item i: status (final, or RLC_PENDING) and the scaled pk / sig in SoA.
 // pks == nullptr: the keys come from the resident table (key_idx[i] < T).
+// SC (k_rlc_items_sc): a signature that decoded DEC_OK is published to the signature cache sc.
+template <bool SC = false>
 BLS_HD BLS_INLINE void rlc_items_lane(uint64_t i, const uint8_t* pks, const uint8_t* sigs, const uint32_t* msg_idx,
                                       uint64_t n, uint64_t n_msgs, const rlc_seed& seed, uint32_t* rpk,
                                       uint32_t* rsig, int32_t* status, const uint32_t* key_idx = nullptr,
                                       uint64_t T = 0, const int32_t* tcode = nullptr, const uint32_t* tab = nullptr,
-                                      const keycache& kc = keycache{}) {
+                                      const keycache& kc = keycache{}, const sigcache& sc = sigcache{}) {
   uint32_t p[36], s[72];
   int st;
   if (msg_idx[i] >= n_msgs || (!pks && key_idx[i] >= T)) {  // device entry point: out-of-range index
@@ -529,12 +620,18 @@ BLS_HD BLS_INLINE void rlc_items_lane(uint64_t i, const uint8_t* pks, const uint
     for (int k = 0; k < 36; ++k) p[k] = (&ip.x.v[0])[k];
     for (int k = 0; k < 72; ++k) s[k] = (&is.x.c0.v[0])[k];
   } else if (pks) {
-    st = rlc_item_kc(pks + 48 * i, sigs + 96 * i, seed, i, p, s, kc);  // kc off: the plain decode (g1_decode_kc_x)
+    if constexpr (SC)
+      st = rlc_item_kc_sc(pks + 48 * i, sigs + 96 * i, seed, i, p, s, kc, sc);
+    else
+      st = rlc_item_kc(pks + 48 * i, sigs + 96 * i, seed, i, p, s, kc);  // kc off: the plain decode (g1_decode_kc_x)
   } else {
     g1a pk;
     g1j xpk;
     const int dp = pubtab_get(pk, xpk, key_idx[i], T, tcode, tab);
-    st = rlc_item_decoded(dp, pk, xpk, sigs + 96 * i, seed, i, p, s);
+    if constexpr (SC)
+      st = rlc_item_decoded_sc(dp, pk, xpk, sigs + 96 * i, seed, i, p, s, sc);
+    else
+      st = rlc_item_decoded(dp, pk, xpk, sigs + 96 * i, seed, i, p, s);
   }
   soa_store<36>(rpk, n, i, p);
   soa_store<72>(rsig, n, i, s);

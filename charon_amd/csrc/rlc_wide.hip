@@ -29,6 +29,7 @@
 
 using bls::keycache;
 using bls::rlc_seed;
+using bls::sigcache;
 constexpr int kWideBlock = 64;  // hipbls.hip kBlock
 
 // Stage 1: one lane per item -> status (final or RLC_PENDING), [r_i] pk_i and [r_i] sig_i in SoA.
@@ -43,6 +44,21 @@ k_rlc_items(uint64_t i0, uint64_t i1, const uint8_t* __restrict__ pks, const uin
   const uint64_t i = i0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i < i1)
     bls::rlc_items_lane(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, rsig, status, key_idx, T, tcode, tab, kc);
+}
+
+// k_rlc_items for a call with the signature cache on (sigcache.h): a lane whose signature decoded
+// DEC_OK, subgroup test included, publishes it in place.  A kernel of its own: with the cache off the call runs
+// k_rlc_items, the kernel it ran before there was a signature cache.
+extern "C" __global__ void __launch_bounds__(kWideBlock) BLS_WIDE_ATTR
+k_rlc_items_sc(uint64_t i0, uint64_t i1, const uint8_t* __restrict__ pks, const uint8_t* __restrict__ sigs,
+               const uint32_t* __restrict__ msg_idx, uint64_t n, uint64_t n_msgs, rlc_seed seed,
+               uint32_t* __restrict__ rpk, uint32_t* __restrict__ rsig, int32_t* __restrict__ status,
+               const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+               const uint32_t* __restrict__ tab, keycache kc, sigcache sc) {
+  const uint64_t i = i0 + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i < i1)
+    bls::rlc_items_lane<true>(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, rsig, status, key_idx, T, tcode, tab, kc,
+                              sc);
 }
 
 // Stage 2: one lane per message to hash -> H(m) in affine SoA (48 words) at its table column.  mlist lists the
@@ -67,4 +83,18 @@ k_rlcb_items(uint64_t n, const uint8_t* __restrict__ pks, const uint8_t* __restr
   if (i < n)
     bls::rlcb_items_lane(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, pts, sc, status, key_idx, T, tcode, tab, g1pos,
                          gpts, gsc, kc);
+}
+
+// k_rlcb_items for a call with the signature cache on, as k_rlc_items_sc.
+extern "C" __global__ void __launch_bounds__(kWideBlock) BLS_WIDE_ATTR
+k_rlcb_items_sc(uint64_t n, const uint8_t* __restrict__ pks, const uint8_t* __restrict__ sigs,
+                const uint32_t* __restrict__ msg_idx, uint64_t n_msgs, rlc_seed seed, uint32_t* __restrict__ rpk,
+                uint32_t* __restrict__ pts, uint32_t* __restrict__ sc, int32_t* __restrict__ status,
+                const uint32_t* __restrict__ key_idx, uint64_t T, const int32_t* __restrict__ tcode,
+                const uint32_t* __restrict__ tab, const uint32_t* __restrict__ g1pos, uint32_t* __restrict__ gpts,
+                uint32_t* __restrict__ gsc, keycache kc, sigcache sgc) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i < n)
+    bls::rlcb_items_lane<true>(i, pks, sigs, msg_idx, n, n_msgs, seed, rpk, pts, sc, status, key_idx, T, tcode, tab,
+                               g1pos, gpts, gsc, kc, sgc);
 }

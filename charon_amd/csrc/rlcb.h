@@ -64,13 +64,16 @@ namespace bls {
 // pts: 2n affine G2 points, point-major (AoS, 48 contiguous words each: sig_i at i, psi(sig_i) at n + i), because
 // the bucket stage gathers them by index -- limb-major SoA made every gathered point 48 separate cache lines
 // (profiles/r04: k_msm_bucket moved 23 GB per launch for 0.8 GB of points); sc: 2n scalars (a_i, then b_i).
+// SC (k_rlcb_items_sc): a signature that decoded DEC_OK is published to the signature cache sgc (sigcache.h).
+template <bool SC = false>
 BLS_HD BLS_INLINE void rlcb_items_lane(uint64_t i, const uint8_t* pks, const uint8_t* sigs, const uint32_t* msg_idx,
                                        uint64_t n, uint64_t n_msgs, const rlc_seed& seed, uint32_t* rpk,
                                        uint32_t* pts, uint32_t* sc, int32_t* status,
                                        const uint32_t* key_idx = nullptr, uint64_t T = 0,
                                        const int32_t* tcode = nullptr, const uint32_t* tab = nullptr,
                                        const uint32_t* g1pos = nullptr, uint32_t* gpts = nullptr,
-                                       uint32_t* gsc = nullptr, const keycache& kc = keycache{}) {
+                                       uint32_t* gsc = nullptr, const keycache& kc = keycache{},
+                                       const sigcache& sgc = sigcache{}) {
   g1j rp;
   jac_set_inf(rp);
   g2a sig, psig;
@@ -91,6 +94,9 @@ BLS_HD BLS_INLINE void rlcb_items_lane(uint64_t i, const uint8_t* pks, const uin
     if (dp == DEC_BAD) st = HIPBLS_ERR_PUBKEY;
     if (st == RLC_PENDING) {
       const int ds = g2_decompress(sig, sigs + 96 * i, true);
+      if constexpr (SC) {
+        if (ds == DEC_OK) sig_publish(sgc, sigs + 96 * i, sig);
+      }
       if (ds == DEC_BAD)
         st = HIPBLS_ERR_SIGNATURE;
       else if (dp == DEC_INF || ds == DEC_INF)

@@ -98,6 +98,8 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_rootcache_stats": ([u64p, u64p, u64p, u64p], ctypes.c_int),
         "hipbls_rootcache_lines_config": ([u64], ctypes.c_int),
         "hipbls_rootcache_lines_stats": ([u64p, u64p, u64p, u64p], ctypes.c_int),
+        "hipbls_sigcache_config": ([u64], ctypes.c_int),
+        "hipbls_sigcache_stats": ([u64p, u64p, u64p, u64p], ctypes.c_int),
         "hipbls_abi_version": ([], ctypes.c_int),
         "hipbls_init": ([ctypes.c_int], ctypes.c_int),
         "hipbls_device_count": ([], ctypes.c_int),
@@ -184,6 +186,7 @@ def exported_symbols() -> List[str]:
         "hipbls_secret_to_public_key_batch_ct_device",
         "hipbls_threshold_split_batch_ct", "hipbls_recover_secret_batch_ct",
         "hipbls_threshold_split_batch_ct_device", "hipbls_recover_secret_batch_ct_device",
+        "hipbls_sigcache_config", "hipbls_sigcache_stats",
     ]
 
 
@@ -849,6 +852,19 @@ class HipBLS:
         a, b, c, d = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self.lib.hipbls_rootcache_lines_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                      ctypes.byref(d)), self.lib)
+        return a.value, b.value, c.value, d.value
+
+    # ---------------------------------------------------------------- resident signature cache (Verify -> sigagg)
+    def sigcache_config(self, slots: int) -> None:
+        """Empty the signature cache and size it to `slots` (rounded up to a power of two; 0 = off, the default)."""
+        _check(self.lib.hipbls_sigcache_config(slots), self.lib)
+
+    def sigcache_stats(self) -> Tuple[int, int, int, int]:
+        """(hits, misses, inserts, rollovers) since the last sigcache_config, summed over contexts: partials sigagg
+        found, partials it did not find, entries the Verify side wrote, generations ended."""
+        a, b, c, d = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self.lib.hipbls_sigcache_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)),
+               self.lib)
         return a.value, b.value, c.value, d.value
 
     # ---------------------------------------------------------------- pairing-check layout

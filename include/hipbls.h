@@ -406,6 +406,23 @@ int hipbls_rootcache_lines_config(uint64_t blocks);
 int hipbls_rootcache_lines_stats(uint64_t* line_hits, uint64_t* blocks_published, uint64_t* pool_full,
                                  uint64_t* check_failures);
 
+/* Device-resident cache of decoded signatures, per context: the 96 wire bytes of a signature -> its affine point.  A
+ * partial signature is verified when it arrives and later handed to sigagg with its duty's other partials; with the
+ * cache on, the Verify side publishes every signature it decoded and proved to lie in G2 (hipbls_verify_batch[_keys]
+ * on the prep + pair routes, hipbls_batch_verify_rlc[_keys], the submission queue's batches on those routes), and
+ * hipbls_threshold_aggregate[_verify]_batch[_keys] looks each partial up before it decompresses and subgroup-tests
+ * it.  Only valid points are entries, an entry checks itself, and a miss runs the code it ran before: outputs and
+ * statuses never depend on the cache.  The one-lane Verify routes, the octet and sixteen-lane latency routes and the
+ * lone sigagg route neither fill nor read it.  `slots` is rounded up to a power of two (256 B each, at least 8, at
+ * most 2^22); 0 turns the cache off, which is the default (or HIPBLS_SIGCACHE_SLOTS): off, every call launches the
+ * kernels it launched before the cache existed.  When half the slots are written, the next Verify-side call first waits
+ * for the device and empties the table (a rollover).  hipbls_sigcache_config waits for the device and empties the
+ * cache and its counters; it may run beside any other call.  Stats are summed over contexts, since the last config:
+ * partials found by sigagg, partials not found, entries written, rollovers.  hipbls_sigcache_stats waits for the
+ * device under each context's lock: a diagnostic. */
+int hipbls_sigcache_config(uint64_t slots);
+int hipbls_sigcache_stats(uint64_t* hits, uint64_t* misses, uint64_t* inserts, uint64_t* rollovers);
+
 /* ------------------------------------------- device-resident variants (inputs already in HBM) ---- */
 /* Same semantics; every pointer is a device pointer; work is enqueued on `stream` (a hipStream_t,
  * NULL = the library's own non-blocking stream of that device, which is NOT ordered with the caller's default

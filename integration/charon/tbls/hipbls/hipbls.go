@@ -134,6 +134,36 @@ func ConfigHCache(capacity uint64) error {
 	return nil
 }
 
+// DefaultSigCacheSlots is the signature cache's size in slots of 256 bytes.  Half the table ends a generation, and
+// half must hold one sigagg call's partials and the next call's, which are verified while the first is aggregated:
+// 2 x 10,000 validators x 7 partials = 140,000 entries, so 280,000 slots, rounded up to 2^19 = 524,288 slots: 128 MiB
+// + 2 MiB per GPU (DESIGN.md 4.14).
+const DefaultSigCacheSlots = 524288
+
+// ConfigSigCache sizes every GPU's resident signature cache (hipbls_sigcache_config): the Verify side publishes every
+// partial signature it decoded and proved to lie in G2, and BatchThresholdAggregate[Verify] looks a partial up before
+// it decompresses and subgroup-tests it again.  0, the library's default, disables the cache.  Results are unchanged
+// by it.
+func ConfigSigCache(slots uint64) error {
+	if rc := C.hipbls_sigcache_config(C.uint64_t(slots)); rc != C.HIPBLS_OK {
+		return devErr(rc)
+	}
+
+	return nil
+}
+
+// SigCacheStats returns the signature cache's counters since the last ConfigSigCache, summed over GPUs: partials
+// sigagg found, partials it did not find, entries the Verify side wrote, and generations ended.  It waits for the
+// devices: a diagnostic.
+func SigCacheStats() (hits, misses, inserts, rollovers uint64, err error) {
+	var h, m, i, r C.uint64_t
+	if rc := C.hipbls_sigcache_stats(&h, &m, &i, &r); rc != C.HIPBLS_OK {
+		return 0, 0, 0, 0, devErr(rc)
+	}
+
+	return uint64(h), uint64(m), uint64(i), uint64(r), nil
+}
+
 // PrefetchRoots hashes signing roots into every GPU's H(m) cache before any signature over them exists
 // (hipbls_hcache_prefetch), so that the first Verify or BatchThresholdAggregateVerify of each root reads H(m) instead
 // of hashing it: the randao root at the start of an epoch, a duty's root once consensus has decided the unsigned data
