@@ -92,6 +92,18 @@ __global__ void k_recover_ct(const uint8_t* shares, const int64_t* ids, const ui
                              int32_t* status, uint8_t* out_pubkeys, int32_t* pk_status, uint8_t* sink);
 }
 
+// PublicKeyShare / PublicKeyRecover in batches (vss.hip: its own translation unit, C linkage).
+extern "C" {
+__global__ void k_vss_dealer_sum(const uint32_t* pts, const int32_t* code, uint32_t n, uint32_t n_dealers,
+                                 uint32_t threshold, uint32_t* out_pts, int32_t* out_code);
+__global__ void k_vss_eval(const uint32_t* pts, const int32_t* code, uint32_t n_val, uint32_t threshold,
+                           const int64_t* ids, uint32_t n_ids, uint8_t* out_pubs, int32_t* status);
+__global__ void k_vss_scale(const uint8_t* shares, const int64_t* ids, const uint64_t* goffs, uint32_t n_groups,
+                            uint32_t n_parts, uint32_t* pts, int32_t* pstat);
+__global__ void k_vss_sum(const uint32_t* pts, const int32_t* pstat, const int64_t* ids, const uint64_t* goffs,
+                          uint32_t n_groups, uint32_t n_parts, uint8_t* out, int32_t* status);
+}
+
 // The eight-lane latency path (verify_lat.hip, its own translation unit: BLS_FP2_PAIR build in namespace bls_fp2p).
 namespace bls_fp2p {
 __global__ void k_verify_prep8(const uint8_t* pks, const uint8_t* msgs, const uint64_t* offs, const uint8_t* sigs,
@@ -362,6 +374,9 @@ struct Context {
   // 64-byte sink that lanes without a store write zeros to, the recover launch's largest group size, and the host
   // calls' public-key outputs.
   DevBuf ct_comb, ct_sink, ct_plan, dl_pub, dl_pst;
+  // PublicKeyShare / PublicKeyRecover (vss.hip): decoded commitments and their codes, the dealers' sums and theirs
+  // (the scaled pubshares of a recover go to vs_pts / vs_code); workspace-ordered (ws_begin / ws_end)
+  DevBuf vs_pts, vs_code, vs_sum, vs_scode;
   int comb_state = 0;  // 0: not built, 1: build enqueued (comb_ev recorded behind it), 2: seen complete
   hipEvent_t comb_ev = nullptr;
   // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
@@ -737,6 +752,7 @@ const KernelRef kKernels[] = {
     KREF(k_root_lookup),
     KREF(k_sign_ct_hash), KREF(k_sign_ct_mul), KREF(k_sk_to_pk_ct),
     KREF(k_g1_comb_build), KREF(k_deal_ct), KREF(k_recover_plan), KREF(k_recover_ct),
+    KREF(k_vss_dealer_sum), KREF(k_vss_eval), KREF(k_vss_scale), KREF(k_vss_sum),
     KREF(k_sigcache_insert), KREF(k_verify_prep_keys_sc), KREF(k_rlc_items_sc), KREF(k_rlcb_items_sc),
     KREF(k_tagg_scale_sc), KREF(k_tv_phase_a_sc), KREF(k_tv_phase_a_keys_sc),
 };
@@ -3556,6 +3572,108 @@ int recover_ct_host(Context& c, const uint8_t* shares, const int64_t* ids, const
   return HIPBLS_OK;
 }
 
+// ---- PublicKeyShare / PublicKeyRecover in batches (vss.hip): public data only ----------------------
+// n_val >= 1 validators; n_val n_dealers threshold points and n_val n_ids lanes below 2^31.  Decode: one lane per
+// commitment (k_g1_decode, unchanged); the dealers' sum: one lane per coefficient, only for a joint dealing; the
+// evaluation: one lane per (validator, id).
+int launch_pk_share(Context& c, const uint8_t* d_commitments, uint64_t n_val, uint32_t n_dealers, uint32_t threshold,
+                    const int64_t* d_ids, uint32_t n_ids, uint8_t* d_pubs, int32_t* d_status, hipStream_t s) {
+  const uint64_t n_coef = n_val * threshold, n_pts = n_coef * n_dealers;
+  HIP_TRY(c.vs_pts.ensure(n_pts * 24 * 4));
+  HIP_TRY(c.vs_code.ensure(n_pts * 4));
+  if (n_dealers > 1) {
+    HIP_TRY(c.vs_sum.ensure(n_coef * 24 * 4));
+    HIP_TRY(c.vs_scode.ensure(n_coef * 4));
+  }
+  int rc = ws_begin(c, s);
+  if (rc) return rc;
+  rc = timed(c, "g1_decode", s, [&] {
+    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)grid_for(n_pts)), dim3(kBlock), 0, s, d_commitments, n_pts,
+                       (uint32_t*)c.vs_pts.p, (int32_t*)c.vs_code.p);
+  });
+  if (rc) return rc;
+  const uint32_t* pts = (const uint32_t*)c.vs_pts.p;
+  const int32_t* code = (const int32_t*)c.vs_code.p;
+  if (n_dealers > 1) {
+    rc = timed(c, "vss_dealer_sum", s, [&] {
+      hipLaunchKernelGGL(k_vss_dealer_sum, dim3((unsigned)grid_for(n_coef)), dim3(kBlock), 0, s, pts, code,
+                         (uint32_t)n_coef, n_dealers, threshold, (uint32_t*)c.vs_sum.p, (int32_t*)c.vs_scode.p);
+    });
+    if (rc) return rc;
+    pts = (const uint32_t*)c.vs_sum.p;
+    code = (const int32_t*)c.vs_scode.p;
+  }
+  rc = timed(c, "vss_eval", s, [&] {
+    hipLaunchKernelGGL(k_vss_eval, dim3((unsigned)grid_for(n_val * n_ids)), dim3(kBlock), 0, s, pts, code,
+                       (uint32_t)n_val, threshold, d_ids, n_ids, d_pubs, d_status);
+  });
+  if (rc) return rc;
+  return ws_end(c, s);
+}
+
+// n_groups >= 1 groups over n_parts pubshares, both below 2^31
+int launch_pk_recover(Context& c, const uint8_t* d_shares, const int64_t* d_ids, const uint64_t* d_goffs,
+                      uint64_t n_groups, uint64_t n_parts, uint8_t* d_out, int32_t* d_status, hipStream_t s) {
+  HIP_TRY(c.vs_pts.ensure((n_parts ? n_parts : 1) * 36 * 4));
+  HIP_TRY(c.vs_code.ensure((n_parts ? n_parts : 1) * 4));
+  int rc = ws_begin(c, s);
+  if (rc) return rc;
+  if (n_parts) {
+    rc = timed(c, "vss_scale", s, [&] {
+      hipLaunchKernelGGL(k_vss_scale, dim3((unsigned)grid_for(n_parts)), dim3(kBlock), 0, s, d_shares, d_ids, d_goffs,
+                         (uint32_t)n_groups, (uint32_t)n_parts, (uint32_t*)c.vs_pts.p, (int32_t*)c.vs_code.p);
+    });
+    if (rc) return rc;
+  }
+  rc = timed(c, "vss_sum", s, [&] {
+    hipLaunchKernelGGL(k_vss_sum, dim3((unsigned)grid_for(n_groups)), dim3(kBlock), 0, s, (const uint32_t*)c.vs_pts.p,
+                       (const int32_t*)c.vs_code.p, d_ids, d_goffs, (uint32_t)n_groups, (uint32_t)n_parts, d_out,
+                       d_status);
+  });
+  if (rc) return rc;
+  return ws_end(c, s);
+}
+
+int pk_share_host(Context& c, const uint8_t* commitments, uint64_t n_val, uint32_t n_dealers, uint32_t threshold,
+                  const int64_t* ids, uint32_t n_ids, uint8_t* out_pubs, int32_t* status) {
+  const uint64_t in_bytes = n_val * n_dealers * threshold * 48, out_bytes = n_val * n_ids * 48;
+  HIP_TRY(c.b_pk.ensure(in_bytes));
+  HIP_TRY(c.b_ids.ensure((uint64_t)n_ids * 8));
+  HIP_TRY(c.b_out.ensure(out_bytes));
+  HIP_TRY(c.b_st.ensure(n_val * 4));
+  HIP_TRY(hipMemcpyAsync(c.b_pk.p, commitments, in_bytes, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipMemcpyAsync(c.b_ids.p, ids, (uint64_t)n_ids * 8, hipMemcpyHostToDevice, c.stream));
+  const int rc = launch_pk_share(c, (const uint8_t*)c.b_pk.p, n_val, n_dealers, threshold, (const int64_t*)c.b_ids.p,
+                                 n_ids, (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p, c.stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out_pubs, c.b_out.p, out_bytes, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_val * 4, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  return HIPBLS_OK;
+}
+
+int pk_recover_host(Context& c, const uint8_t* shares, const int64_t* ids, const uint64_t* goffs, uint64_t n_groups,
+                    uint8_t* out_pubkeys, int32_t* status) {
+  const uint64_t n_parts = goffs[n_groups];
+  HIP_TRY(c.b_pk.ensure((n_parts ? n_parts : 1) * 48));
+  HIP_TRY(c.b_ids.ensure((n_parts ? n_parts : 1) * 8));
+  HIP_TRY(c.b_off.ensure((n_groups + 1) * 8));
+  HIP_TRY(c.b_out.ensure(n_groups * 48));
+  HIP_TRY(c.b_st.ensure(n_groups * 4));
+  if (n_parts) {
+    HIP_TRY(hipMemcpyAsync(c.b_pk.p, shares, n_parts * 48, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.b_ids.p, ids, n_parts * 8, hipMemcpyHostToDevice, c.stream));
+  }
+  HIP_TRY(hipMemcpyAsync(c.b_off.p, goffs, (n_groups + 1) * 8, hipMemcpyHostToDevice, c.stream));
+  const int rc = launch_pk_recover(c, (const uint8_t*)c.b_pk.p, (const int64_t*)c.b_ids.p, (const uint64_t*)c.b_off.p,
+                                   n_groups, n_parts, (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p, c.stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out_pubkeys, c.b_out.p, n_groups * 48, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_groups * 4, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  return HIPBLS_OK;
+}
+
 int fav_host(Context& c, const uint8_t* pks, const uint64_t* koffs, uint64_t n_groups, const uint8_t* sigs,
              const uint8_t* msgs, const uint64_t* moffs, int32_t* status) {
   const uint64_t nkeys = koffs[n_groups], msg_total = moffs[n_groups];
@@ -4513,6 +4631,81 @@ int hipbls_recover_secret(const uint8_t* shares, const int64_t* ids, uint32_t n,
   if (!out_secret || !status || (n && (!shares || !ids))) return arg_err("bad recover arguments");
   const uint64_t offs[2] = {0, n};
   return hipbls_recover_secret_batch_ct(shares, ids, offs, 1, out_secret, status, nullptr, nullptr);
+}
+
+// PublicKeyShare / PublicKeyRecover in batches.  Every lane and item count stays below 2^31 (the
+// kernels' 32-bit lane indices); the validators / groups of a host call are split over the contexts whole.
+constexpr uint64_t kSplitVss = 256;            // validators per context range
+constexpr uint32_t kVssMaxThreshold = 65535;  // vss.h VSS_MAX_THRESHOLD
+
+bool pk_share_args_ok(const void* commitments, uint64_t n_val, uint32_t n_dealers, uint32_t threshold, const void* ids,
+                      uint32_t n_ids, const void* out_pubs, const void* status) {
+  if (!commitments || !ids || !out_pubs || !status || threshold > kVssMaxThreshold) return false;
+  const uint64_t per = (uint64_t)n_dealers * threshold;  // below 2^48
+  if (per >= kDealMaxLanes || n_val >= kDealMaxLanes || n_ids >= kDealMaxLanes) return false;
+  return n_val * per < kDealMaxLanes && n_val * n_ids < kDealMaxLanes;  // factors below 2^31: no overflow
+}
+
+int hipbls_public_key_share_batch(const uint8_t* commitments, uint64_t n_val, uint32_t n_dealers, uint32_t threshold,
+                                  const int64_t* ids, uint32_t n_ids, uint8_t* out_pubs, int32_t* status) {
+  if (threshold == 0 || n_dealers == 0 || n_ids == 0) return arg_err("bad public key share arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!pk_share_args_ok(commitments, n_val, n_dealers, threshold, ids, n_ids, out_pubs, status))
+    return arg_err("bad public key share arguments");
+  ENSURE_INIT();
+  const uint64_t in_row = 48 * (uint64_t)n_dealers * threshold, out_row = 48 * (uint64_t)n_ids;
+  return run_ranges(plan_ranges(n_val, parts_for(n_val, kSplitVss), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      return pk_share_host(c, commitments + in_row * lo, hi - lo, n_dealers, threshold, ids, n_ids,
+                                           out_pubs + out_row * lo, status + lo);
+                    });
+}
+
+int hipbls_public_key_share_batch_device(const uint8_t* d_commitments, uint64_t n_val, uint32_t n_dealers,
+                                         uint32_t threshold, const int64_t* d_ids, uint32_t n_ids, uint8_t* d_out_pubs,
+                                         int32_t* d_status, void* stream) {
+  if (threshold == 0 || n_dealers == 0 || n_ids == 0) return arg_err("bad public key share arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!pk_share_args_ok(d_commitments, n_val, n_dealers, threshold, d_ids, n_ids, d_out_pubs, d_status))
+    return arg_err("bad public key share arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_pk_share(c, d_commitments, n_val, n_dealers, threshold, d_ids, n_ids, d_out_pubs, d_status, s);
+}
+
+int hipbls_public_key_recover_batch(const uint8_t* pubshares, const int64_t* ids, const uint64_t* group_offsets,
+                                    uint64_t n_groups, uint8_t* out_pubkeys, int32_t* status) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!group_offsets || !out_pubkeys || !status || n_groups >= kDealMaxLanes)
+    return arg_err("bad public key recover arguments");
+  if (!groups_ok(group_offsets, n_groups)) return arg_err("bad group offsets");
+  const uint64_t n_parts = group_offsets[n_groups];
+  if ((n_parts && (!pubshares || !ids)) || n_parts >= kDealMaxLanes) return arg_err("bad public key recover arguments");
+  ENSURE_INIT();
+  return run_ranges(plan_ranges(n_groups, parts_for(n_groups, kSplitGroups), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      std::vector<uint64_t> tmp;
+                      const uint64_t p0 = group_offsets[lo];
+                      return pk_recover_host(c, pubshares ? pubshares + 48 * p0 : pubshares, ids ? ids + p0 : ids,
+                                             rebase(group_offsets, lo, hi, tmp), hi - lo, out_pubkeys + 48 * lo,
+                                             status + lo);
+                    });
+}
+
+int hipbls_public_key_recover_batch_device(const uint8_t* d_pubshares, const int64_t* d_ids,
+                                           const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
+                                           uint8_t* d_out_pubkeys, int32_t* d_status, void* stream) {
+  if (n_groups == 0) return HIPBLS_OK;
+  if (!d_group_offsets || !d_out_pubkeys || !d_status || (n_parts && (!d_pubshares || !d_ids)) ||
+      n_groups >= kDealMaxLanes || n_parts >= kDealMaxLanes)
+    return arg_err("bad public key recover arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_pk_recover(c, d_pubshares, d_ids, d_group_offsets, n_groups, n_parts, d_out_pubkeys, d_status, s);
 }
 
 int hipbls_kernel_timing(const char* name, double* avg_ms, uint64_t* launches) {

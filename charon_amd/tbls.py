@@ -127,6 +127,12 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_threshold_split_batch_ct_device": ([vp, vp, u64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp],
                                                    ctypes.c_int),
         "hipbls_recover_secret_batch_ct_device": ([vp, vp, vp, u64, u64, vp, vp, vp, vp, vp], ctypes.c_int),
+        "hipbls_public_key_share_batch": ([u8p, u64, ctypes.c_uint32, ctypes.c_uint32, i64p, ctypes.c_uint32, u8p, i32p],
+                                          ctypes.c_int),
+        "hipbls_public_key_recover_batch": ([u8p, i64p, u64p, u64, u8p, i32p], ctypes.c_int),
+        "hipbls_public_key_share_batch_device": ([vp, u64, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp,
+                                                  vp], ctypes.c_int),
+        "hipbls_public_key_recover_batch_device": ([vp, vp, vp, u64, u64, vp, vp, vp], ctypes.c_int),
         "hipbls_batch_verify_rlc": ([u8p, u8p, u32p, u64, u8p, u64p, u64, u8p, i32p], ctypes.c_int),
         "hipbls_batch_verify_rlc_device": ([vp, vp, vp, u64, vp, vp, u64, u8p, vp, vp], ctypes.c_int),
         "hipbls_rlc_stats": ([u64p, u64p, u64p], ctypes.c_int),
@@ -187,6 +193,8 @@ def exported_symbols() -> List[str]:
         "hipbls_threshold_split_batch_ct", "hipbls_recover_secret_batch_ct",
         "hipbls_threshold_split_batch_ct_device", "hipbls_recover_secret_batch_ct_device",
         "hipbls_sigcache_config", "hipbls_sigcache_stats",
+        "hipbls_public_key_share_batch", "hipbls_public_key_recover_batch",
+        "hipbls_public_key_share_batch_device", "hipbls_public_key_recover_batch_device",
     ]
 
 
@@ -368,6 +376,85 @@ class HipBLS:
             return secs, list(st)[:n], None, None
         praw = pks.raw
         return secs, list(st)[:n], [praw[48 * g:48 * g + 48] for g in range(n)], list(pst)[:n]
+
+    # ---------------------------------------------------------------- the public half of the threshold API
+    def public_key_share_batch(self, commitments: Sequence[Sequence[Sequence[bytes]]],
+                               ids: Sequence[int]) -> Tuple[List[List[bytes]], List[int]]:
+        """herumi's blsPublicKeyShare for many validators (hipbls_public_key_share_batch): commitments[v][d][j] is
+        dealer d's commitment to coefficient j of validator v's polynomial (48-byte keys; the dealers' polynomials
+        are added), ids the evaluation points shared by every validator.  Returns (pubs, status): pubs[v][i] is the
+        public polynomial of v at ids[i] (id 0: the group public key), status[v] OK or ERR_PUBKEY (a commitment
+        does not decode; its outputs are zero bytes)."""
+        n = len(commitments)
+        ids = [_go_int(i) for i in ids]
+        n_dealers = len(commitments[0]) if n else 1
+        threshold = len(commitments[0][0]) if n and n_dealers else 1
+        flat = []
+        for val in commitments:
+            if len(val) != n_dealers:
+                raise ValueError("every validator has the same number of dealers")
+            for poly in val:
+                if len(poly) != threshold:
+                    raise ValueError("every polynomial has threshold commitments")
+                flat.extend(poly)
+        _check_lengths("commitments", flat, 48)
+        m = len(ids)
+        arr = (ctypes.c_int64 * max(m, 1))(*ids)
+        out = ctypes.create_string_buffer(48 * max(n * m, 1))
+        st = _status_array(n)
+        _check(self.lib.hipbls_public_key_share_batch(b"".join(flat), n, n_dealers, threshold, arr, m, out, st),
+               self.lib)
+        raw = out.raw
+        return [[raw[48 * (m * v + i):48 * (m * v + i) + 48] for i in range(m)] for v in range(n)], list(st)[:n]
+
+    def public_key_recover_batch(self, groups: Sequence[Mapping[int, bytes]]) -> Tuple[List[bytes], List[int]]:
+        """herumi's blsPublicKeyRecover for many groups (hipbls_public_key_recover_batch): group g is a
+        {share id: pubshare} map (or a sequence of (id, pubshare) pairs).  Returns (pubkeys, status): status[g] OK,
+        ERR_COMBINE (empty group, id 0, duplicate id) or ERR_PUBKEY (a pubshare does not decode); zero bytes unless
+        OK."""
+        n = len(groups)
+        ids, shares, offs = [], [], (ctypes.c_uint64 * (n + 1))()
+        for g, grp in enumerate(groups):
+            offs[g] = len(ids)
+            for i, sh in (grp.items() if hasattr(grp, "items") else grp):
+                ids.append(_go_int(i))
+                shares.append(sh)
+        offs[n] = len(ids)
+        _check_lengths("pubshares", shares, 48)
+        arr = (ctypes.c_int64 * max(len(ids), 1))(*ids)
+        out = ctypes.create_string_buffer(48 * max(n, 1))
+        st = _status_array(n)
+        _check(self.lib.hipbls_public_key_recover_batch(b"".join(shares), arr, offs, n, out, st), self.lib)
+        raw = out.raw
+        return [raw[48 * g:48 * g + 48] for g in range(n)], list(st)[:n]
+
+    def verify_secret_shares(self, shares: Sequence[bytes], commitments: Sequence[Sequence[bytes]],
+                             my_id: int) -> List[bool]:
+        """The Feldman check of received shares: shares[d] is what dealer d sent this node (operator id my_id) and
+        commitments[d] that dealer's commitments to its polynomial.  True where [share] g1 equals the dealer's
+        public polynomial at my_id.  Both sides are public values: [share] g1 comes from the secret-independent
+        secret_to_public_key_batch_ct."""
+        if len(shares) != len(commitments):
+            raise ValueError("one commitment list per share")
+        if not shares:
+            return []
+        pks, st = self.secret_to_public_key_batch_ct(shares)
+        want, wst = self.public_key_share_batch([[list(c)] for c in commitments], [my_id])
+        return [st[d] == OK and wst[d] == OK and pks[d] == want[d][0] for d in range(len(shares))]
+
+    def verify_pubshares(self, pubkey: bytes, pubshares: Mapping[int, bytes], threshold: int) -> bool:
+        """Whether every pubshare lies on the one polynomial of degree threshold - 1 through pubkey (its value at 0).
+        One public_key_recover_batch call: the first `threshold` shares recover pubkey; for every further share k the
+        same shares with ids shifted to id - k recover that share (Lagrange at k over x_j is Lagrange at 0 over
+        x_j - k)."""
+        items = list(pubshares.items())
+        if threshold < 1 or len(items) < threshold:
+            return False
+        base, rest = items[:threshold], items[threshold:]
+        groups = [base] + [[(i - k, p) for i, p in base] for k, _ in rest]
+        got, st = self.public_key_recover_batch(groups)
+        want = [pubkey] + [p for _, p in rest]
+        return all(s == OK for s in st) and got == want
 
     def _split(self, secret: bytes, total: int, threshold: int, tail: Sequence[bytes]) -> Dict[int, bytes]:
         """One validator of threshold_split_batch_ct.  Exceptions and texts are those of the former single call; in

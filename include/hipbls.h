@@ -293,6 +293,37 @@ int hipbls_recover_secret_batch_ct(const uint8_t* shares, const int64_t* ids, co
                                    uint64_t n_groups, uint8_t* out_secrets, int32_t* status,
                                    uint8_t* out_pubkeys, int32_t* pk_status);
 
+/* herumi blsPublicKeyShare, for many validators and many ids, with joint dealings (public data only).
+ * Coefficient j of validator v is  A[v][j] = sum over d < n_dealers of C[v][d][j],
+ * C[v][d][j] = commitments[48 ((v n_dealers + d) threshold + j) ..] (compressed G1, decoded with the subgroup test).
+ * out_pubs[48 (v n_ids + i) ..] = sum_j [x_i^j] A[v][j],  x_i = ids[i] mod r (ids as in ThresholdAggregate).
+ * status[v] = OK | ERR_PUBKEY (any commitment of v does not decode: all n_ids outputs of v are zero bytes).
+ * Evaluation ids: one list, shared by every validator of the call (the cluster's operator indices).  Duplicate ids
+ * are allowed (the same output twice).  An id that is 0 mod r is allowed: its output is A[v][0], the validator's group
+ * public key -- a joint dealing's root key without host arithmetic.  Negative ids and INT64_MIN work:
+ * [x] P = -[|x|] P with |x| <= 2^63.
+ * Infinity: a commitment with the valid infinity encoding (0xc0 then 47 zero bytes) is the identity and takes part in
+ * the arithmetic (a polynomial whose top coefficient is 0 is a legal dealing); an output that is the identity is
+ * written as that encoding with status OK -- the caller decides what an identity key means.
+ * n_val == 0 is OK.  HIPBLS_ERR_ARG: threshold == 0, n_dealers == 0, n_ids == 0, a null pointer with a non-zero
+ * count, threshold > 65,535, or n_val, n_ids, n_val n_ids or n_val n_dealers threshold >= 2^31.  Validators are split
+ * over the contexts whole.  Kernels: one lane per commitment (timed as g1_decode), for n_dealers > 1 one lane per
+ * (v, j) (vss_dealer_sum), one lane per (v, i) (vss_eval); every addition is the complete one. */
+int hipbls_public_key_share_batch(const uint8_t* commitments, uint64_t n_val, uint32_t n_dealers, uint32_t threshold,
+                                  const int64_t* ids, uint32_t n_ids, uint8_t* out_pubs, int32_t* status);
+
+/* herumi blsPublicKeyRecover for many groups.  Group g: pubshares[48 k ..], ids[k] for k in
+ * [group_offsets[g], group_offsets[g+1]).  out_pubkeys[48 g ..] = sum_k lambda_k P_k (Lagrange at 0).
+ * status[g] = OK | ERR_COMBINE (empty group, id = 0 mod r, duplicate id: decided first, as
+ * hipbls_recover_secret_batch_ct does) | ERR_PUBKEY (a pubshare does not decode).  Zero bytes on error.
+ * Infinity: a pubshare with the valid infinity encoding is the identity and takes part; an identity result is written
+ * as 0xc0 then 47 zero bytes with status OK.  n_groups == 0 is OK; a null pointer with a non-zero count, or n_groups
+ * or the pubshare count >= 2^31, is HIPBLS_ERR_ARG.  Groups are split over the contexts whole.  Kernels: one lane per
+ * pubshare (vss_scale: decode, then the short integer multiple of ThresholdAggregate's small-id path or the full
+ * Lagrange coefficient off it), one lane per group (vss_sum). */
+int hipbls_public_key_recover_batch(const uint8_t* pubshares, const int64_t* ids, const uint64_t* group_offsets,
+                                    uint64_t n_groups, uint8_t* out_pubkeys, int32_t* status);
+
 /* Random-linear-combination BatchVerify.  Item i is (pks[48 i..], message msg_idx[i], sigs[96 i..]);
  * message m is msgs[msg_offsets[m] .. msg_offsets[m+1]) (n_msgs distinct messages, each hashed once).
  * status[i] is exactly hipbls_verify_batch's (i.e. tbls.Verify's) outcome for the item: items are
@@ -503,6 +534,14 @@ int hipbls_recover_secret_batch_ct_device(const uint8_t* d_shares, const int64_t
                                           const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
                                           uint8_t* d_out_secrets, int32_t* d_status, uint8_t* d_out_pubkeys,
                                           int32_t* d_pk_status, void* stream);
+/* As hipbls_public_key_share_batch / hipbls_public_key_recover_batch on device buffers: they only enqueue (on the
+ * context that owns d_status), with the same argument rules; n_parts is the pubshare count, group_offsets[n_groups]. */
+int hipbls_public_key_share_batch_device(const uint8_t* d_commitments, uint64_t n_val, uint32_t n_dealers,
+                                         uint32_t threshold, const int64_t* d_ids, uint32_t n_ids, uint8_t* d_out_pubs,
+                                         int32_t* d_status, void* stream);
+int hipbls_public_key_recover_batch_device(const uint8_t* d_pubshares, const int64_t* d_ids,
+                                           const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
+                                           uint8_t* d_out_pubkeys, int32_t* d_status, void* stream);
 
 /* As hipbls_batch_verify_rlc; seed32 is a host pointer.  An out-of-range msg_idx[i] yields
  * status[i] = HIPBLS_ERR_ARG. */

@@ -9,6 +9,7 @@ import "C"
 
 import (
 	"crypto/rand"
+	"sort"
 	"unsafe"
 
 	"github.com/obolnetwork/charon/app/errors"
@@ -405,4 +406,175 @@ func (HipBLS) BatchRecoverSecret(groups []map[int]tbls.PrivateKey) ([]tbls.Priva
 	observe("recover_secret", errs)
 
 	return secrets, pks, errs, nil
+}
+
+// PublicKeyShares evaluates every validator's public polynomial at every id in one call (herumi's blsPublicKeyShare;
+// hipbls_public_key_share_batch).  commitments[v][d][j] is dealer d's Feldman commitment to coefficient j of validator
+// v's polynomial; the dealers' polynomials are added, so a joint dealing (FROST) needs no host arithmetic.  ids are the
+// cluster's operator indices, shared by every validator; id 0 gives the validator's group public key.  out[v][i] is
+// the key at ids[i]; errs[v] is set when a commitment of v does not deserialize.  Not a method of tbls.Implementation.
+func (HipBLS) PublicKeyShares(commitments [][][]tbls.PublicKey, ids []int) ([][]tbls.PublicKey, []error, error) {
+	n := len(commitments)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	dealers := len(commitments[0])
+	if dealers == 0 || len(commitments[0][0]) == 0 || len(ids) == 0 {
+		return nil, nil, errors.New("public key shares need a dealer, a commitment and an id")
+	}
+	threshold := len(commitments[0][0])
+	flat := make([]byte, 0, 48*n*dealers*threshold)
+	for _, val := range commitments {
+		if len(val) != dealers {
+			return nil, nil, errors.New("every validator has the same number of dealers")
+		}
+		for _, poly := range val {
+			if len(poly) != threshold {
+				return nil, nil, errors.New("every polynomial has threshold commitments")
+			}
+			for _, c := range poly {
+				flat = append(flat, c[:]...)
+			}
+		}
+	}
+	xs := make([]int64, len(ids))
+	for i, id := range ids {
+		xs[i] = int64(id)
+	}
+	pubs := make([]byte, 48*n*len(ids))
+	status := make([]int32, n)
+	if rc := C.hipbls_public_key_share_batch(u8(flat), C.uint64_t(n), C.uint32_t(dealers), C.uint32_t(threshold),
+		i64(xs), C.uint32_t(len(ids)), u8(pubs), i32(status)); rc != C.HIPBLS_OK {
+		return nil, nil, observeFailure("public_key_share", n, devErr(rc))
+	}
+	out := make([][]tbls.PublicKey, n)
+	errs := make([]error, n)
+	for v := range commitments {
+		if status[v] != C.HIPBLS_OK {
+			errs[v] = errors.New("cannot set compressed public key in Herumi format")
+			continue
+		}
+		out[v] = make([]tbls.PublicKey, len(ids))
+		for i := range ids {
+			copy(out[v][i][:], pubs[48*(v*len(ids)+i):])
+		}
+	}
+	observe("public_key_share", errs)
+
+	return out, errs, nil
+}
+
+// RecoverPublicKeys recovers one public key per group of pubshares in one call (herumi's blsPublicKeyRecover: Lagrange
+// at 0 over G1; hipbls_public_key_recover_batch).  errs[g] is set for an empty group, a share index 0 or a pubshare that
+// does not deserialize.  Not a method of tbls.Implementation.
+func (HipBLS) RecoverPublicKeys(groups []map[int]tbls.PublicKey) ([]tbls.PublicKey, []error, error) {
+	n := len(groups)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	var flat []byte
+	var ids []int64
+	offs := []uint64{0}
+	for _, g := range groups {
+		for idx, k := range g {
+			flat = append(flat, k[:]...)
+			ids = append(ids, int64(idx))
+		}
+		offs = append(offs, uint64(len(ids)))
+	}
+	pks := make([]tbls.PublicKey, n)
+	status := make([]int32, n)
+	if rc := C.hipbls_public_key_recover_batch(u8(flat), i64(ids), u64(offs), C.uint64_t(n),
+		(*C.uint8_t)(unsafe.Pointer(&pks[0][0])), i32(status)); rc != C.HIPBLS_OK {
+		return nil, nil, observeFailure("public_key_recover", n, devErr(rc))
+	}
+	errs := make([]error, n)
+	for g := range groups {
+		switch {
+		case status[g] == C.HIPBLS_ERR_PUBKEY:
+			errs[g] = errors.New("cannot set compressed public key in Herumi format")
+		case status[g] != C.HIPBLS_OK:
+			errs[g] = errors.New("cannot recover public key from public key shares")
+		}
+	}
+	observe("public_key_recover", errs)
+
+	return pks, errs, nil
+}
+
+// VerifySecretShares is the Feldman check of received shares: shares[d] is what dealer d sent this node (operator index
+// myID) and commitments[d] that dealer's commitments to its polynomial.  ok[d] says whether [shares[d]] g1 equals the
+// dealer's public polynomial at myID.  Both sides are public values; [share] g1 comes from the secret-independent
+// kernel (hipbls_secret_to_public_key_batch_ct).
+func (h HipBLS) VerifySecretShares(shares []tbls.PrivateKey, commitments [][]tbls.PublicKey, myID int) ([]bool, error) {
+	n := len(shares)
+	if n != len(commitments) {
+		return nil, errors.New("one commitment list per share")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	flat := make([]byte, 0, 32*n)
+	polys := make([][][]tbls.PublicKey, n)
+	for d, s := range shares {
+		flat = append(flat, s[:]...)
+		polys[d] = [][]tbls.PublicKey{commitments[d]}
+	}
+	pks := make([]tbls.PublicKey, n)
+	status := make([]int32, n)
+	if rc := C.hipbls_secret_to_public_key_batch_ct(u8(flat), C.uint64_t(n), (*C.uint8_t)(unsafe.Pointer(&pks[0][0])),
+		i32(status)); rc != C.HIPBLS_OK {
+		return nil, observeFailure("public_key_share", n, devErr(rc))
+	}
+	want, errs, err := h.PublicKeyShares(polys, []int{myID})
+	if err != nil {
+		return nil, err
+	}
+	ok := make([]bool, n)
+	for d := range shares {
+		ok[d] = status[d] == C.HIPBLS_OK && errs[d] == nil && pks[d] == want[d][0]
+	}
+
+	return ok, nil
+}
+
+// VerifyPubShares says whether every pubshare lies on the one polynomial of degree threshold-1 whose value at 0 is
+// pubkey, in one RecoverPublicKeys call: the threshold pubshares with the smallest indices must recover pubkey, and for
+// every further index k the same pubshares at indices shifted to idx-k must recover pubshares[k] (Lagrange at k over
+// x_j is Lagrange at 0 over x_j-k).
+func (h HipBLS) VerifyPubShares(pubkey tbls.PublicKey, pubshares map[int]tbls.PublicKey, threshold int) (bool, error) {
+	if threshold < 1 || len(pubshares) < threshold {
+		return false, nil
+	}
+	idxs := make([]int, 0, len(pubshares))
+	for idx := range pubshares {
+		idxs = append(idxs, idx)
+	}
+	sort.Ints(idxs)
+	base, rest := idxs[:threshold], idxs[threshold:]
+	groups := make([]map[int]tbls.PublicKey, 0, 1+len(rest))
+	want := make([]tbls.PublicKey, 0, 1+len(rest))
+	for _, k := range append([]int{0}, rest...) {
+		g := make(map[int]tbls.PublicKey, threshold)
+		for _, idx := range base {
+			g[idx-k] = pubshares[idx]
+		}
+		groups = append(groups, g)
+		if len(want) == 0 {
+			want = append(want, pubkey)
+		} else {
+			want = append(want, pubshares[k])
+		}
+	}
+	got, errs, err := h.RecoverPublicKeys(groups)
+	if err != nil {
+		return false, err
+	}
+	for g := range groups {
+		if errs[g] != nil || got[g] != want[g] {
+			return false, nil
+		}
+	}
+
+	return true, nil
 }
