@@ -104,6 +104,17 @@ __global__ void k_vss_sum(const uint32_t* pts, const int32_t* pstat, const int64
                           uint32_t n_groups, uint32_t n_parts, uint8_t* out, int32_t* status);
 }
 
+// A joint-Feldman dealing round in batches (dkg_ct.hip: its own translation unit, C linkage).
+extern "C" {
+__global__ void k_commit_ct(const uint8_t* secrets, const uint8_t* tails, uint32_t n, uint32_t threshold,
+                            const uint32_t* T, uint8_t* out_commitments, int32_t* com_status, uint8_t* sink);
+__global__ void k_share_check_ct(const uint8_t* shares, const uint8_t* expected, const int32_t* decode_status,
+                                 uint32_t n, const uint32_t* T, int32_t* status, uint8_t* sink);
+__global__ void k_share_sum_ct(const uint8_t* shares, const uint8_t* include, uint32_t include_stride, uint32_t n_val,
+                               uint32_t n_dealers, const uint32_t* T, uint8_t* out_shares, int32_t* status,
+                               uint8_t* out_pubs, int32_t* pub_status, uint8_t* sink);
+}
+
 // The eight-lane latency path (verify_lat.hip, its own translation unit: BLS_FP2_PAIR build in namespace bls_fp2p).
 namespace bls_fp2p {
 __global__ void k_verify_prep8(const uint8_t* pks, const uint8_t* msgs, const uint64_t* offs, const uint8_t* sigs,
@@ -377,6 +388,9 @@ struct Context {
   // PublicKeyShare / PublicKeyRecover (vss.hip): decoded commitments and their codes, the dealers' sums and theirs
   // (the scaled pubshares of a recover go to vs_pts / vs_code); workspace-ordered (ws_begin / ws_end)
   DevBuf vs_pts, vs_code, vs_sum, vs_scode;
+  // The receiver's share check (dkg_ct.hip): the receiver's id, the commitments evaluated at it and their decode
+  // status, one entry per (validator, dealer): public, workspace-ordered with the buffers above
+  DevBuf dk_id, dk_exp, dk_code;
   int comb_state = 0;  // 0: not built, 1: build enqueued (comb_ev recorded behind it), 2: seen complete
   hipEvent_t comb_ev = nullptr;
   // the keyed Verify latency route (verify_keys_lat) from the host call: message indices, cache columns, miss list,
@@ -753,6 +767,7 @@ const KernelRef kKernels[] = {
     KREF(k_sign_ct_hash), KREF(k_sign_ct_mul), KREF(k_sk_to_pk_ct),
     KREF(k_g1_comb_build), KREF(k_deal_ct), KREF(k_recover_plan), KREF(k_recover_ct),
     KREF(k_vss_dealer_sum), KREF(k_vss_eval), KREF(k_vss_scale), KREF(k_vss_sum),
+    KREF(k_commit_ct), KREF(k_share_check_ct), KREF(k_share_sum_ct),
     KREF(k_sigcache_insert), KREF(k_verify_prep_keys_sc), KREF(k_rlc_items_sc), KREF(k_rlcb_items_sc),
     KREF(k_tagg_scale_sc), KREF(k_tv_phase_a_sc), KREF(k_tv_phase_a_keys_sc),
 };
@@ -3674,6 +3689,157 @@ int pk_recover_host(Context& c, const uint8_t* shares, const int64_t* ids, const
   return HIPBLS_OK;
 }
 
+// ---- a joint-Feldman dealing round in batches (dkg_ct.hip) -----------------------------------------
+// n_val >= 1 validators, n_val threshold lanes below 2^31
+int launch_commit_ct(Context& c, const uint8_t* d_secrets, const uint8_t* d_tails, uint64_t n_val, uint32_t threshold,
+                     uint8_t* d_com, int32_t* d_cst, hipStream_t s) {
+  int rc = ensure_comb(c, s);
+  if (rc) return rc;
+  const uint32_t n = (uint32_t)(n_val * threshold);
+  return timed(c, "commit_ct", s, [&] {
+    hipLaunchKernelGGL(k_commit_ct, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_secrets, d_tails, n, threshold,
+                       (const uint32_t*)c.ct_comb.p, d_com, d_cst, (uint8_t*)c.ct_sink.p);
+  });
+}
+
+// n = n_val n_dealers >= 1 lanes, n threshold below 2^31.  Each (v, d) is a one-dealer validator of the share call,
+// evaluated at my_id (which reaches the device by two stream-ordered word fills: nothing of the host's is read later);
+// the check then compares on the same stream.  The expected bytes and their status stay in the context's workspace.
+int launch_share_check(Context& c, const uint8_t* d_shares, const uint8_t* d_commitments, uint64_t n, uint32_t threshold,
+                       int64_t my_id, int32_t* d_status, hipStream_t s) {
+  HIP_TRY(c.dk_id.ensure(8));
+  HIP_TRY(c.dk_exp.ensure(n * 48));
+  HIP_TRY(c.dk_code.ensure(n * 4));
+  int rc = ensure_comb(c, s);
+  if (rc) return rc;
+  rc = ws_begin(c, s);
+  if (rc) return rc;
+  const uint64_t id = (uint64_t)my_id;
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c.dk_id.p, (int)(uint32_t)id, 1, s));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)((uint8_t*)c.dk_id.p + 4), (int)(uint32_t)(id >> 32), 1, s));
+  rc = launch_pk_share(c, d_commitments, n, 1, threshold, (const int64_t*)c.dk_id.p, 1, (uint8_t*)c.dk_exp.p,
+                       (int32_t*)c.dk_code.p, s);
+  if (rc) return rc;
+  rc = timed(c, "share_check_ct", s, [&] {
+    hipLaunchKernelGGL(k_share_check_ct, dim3((unsigned)grid_for(n)), dim3(kBlock), 0, s, d_shares,
+                       (const uint8_t*)c.dk_exp.p, (const int32_t*)c.dk_code.p, (uint32_t)n,
+                       (const uint32_t*)c.ct_comb.p, d_status, (uint8_t*)c.ct_sink.p);
+  });
+  if (rc) return rc;
+  return ws_end(c, s);
+}
+
+// n_val >= 1 validators, n_val n_dealers below 2^31.  d_include null: every dealer.  d_pubs / d_pst both null or given.
+int launch_share_sum(Context& c, const uint8_t* d_shares, const uint8_t* d_include, uint64_t n_val, uint32_t n_dealers,
+                     uint8_t* d_out, int32_t* d_status, uint8_t* d_pubs, int32_t* d_pst, hipStream_t s) {
+  int rc = ensure_comb(c, s);
+  if (rc) return rc;
+  // without a mask the kernel reads one byte of the sink with a stride of 0 and overrides it
+  const uint8_t* const inc = d_include ? d_include : (const uint8_t*)c.ct_sink.p;
+  const uint32_t stride = d_include ? 1u : 0u;
+  return timed(c, "share_sum_ct", s, [&] {
+    hipLaunchKernelGGL(k_share_sum_ct, dim3((unsigned)grid_for(n_val)), dim3(kBlock), 0, s, d_shares, inc, stride,
+                       (uint32_t)n_val, n_dealers, (const uint32_t*)c.ct_comb.p, d_out, d_status, d_pubs, d_pst,
+                       (uint8_t*)c.ct_sink.p);
+  });
+}
+
+// The end of a host form that held secrets on the device: after the body, whatever it returned, the wipes are enqueued
+// and the stream is drained (deal_ct_host's order).
+int finish_wiped(Context& c, int rc, std::initializer_list<std::pair<void*, uint64_t>> wipes) {
+  const std::string err = g_last_error;
+  hipError_t w = hipSuccess;
+  for (const auto& b : wipes)
+    if (b.second) {
+      const hipError_t e = hipMemsetAsync(b.first, 0, b.second, c.stream);
+      if (w == hipSuccess) w = e;
+    }
+  const hipError_t sy = hipStreamSynchronize(c.stream);
+  if (rc) {
+    g_last_error = err;
+    return rc;
+  }
+  HIP_TRY(w);
+  HIP_TRY(sy);
+  return HIPBLS_OK;
+}
+
+int deal_commit_host(Context& c, const uint8_t* secrets, const uint8_t* tails, uint64_t n_val, uint32_t total,
+                     uint32_t threshold, uint8_t* out_shares, int32_t* status, uint8_t* out_com, int32_t* com_status) {
+  const uint64_t tail_bytes = n_val * 32 * (uint64_t)(threshold - 1), share_bytes = n_val * (uint64_t)total * 32;
+  const uint64_t n_com = n_val * threshold;
+  HIP_TRY(c.b_pk.ensure(n_val * 32));
+  HIP_TRY(c.b_aux.ensure(tail_bytes ? tail_bytes : 1));
+  HIP_TRY(c.b_out.ensure(share_bytes));
+  HIP_TRY(c.b_st.ensure(n_val * 4));
+  HIP_TRY(c.dl_pub.ensure(n_com * 48));
+  HIP_TRY(c.dl_pst.ensure(n_com * 4));
+  auto body = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(c.b_pk.p, secrets, n_val * 32, hipMemcpyHostToDevice, c.stream));
+    if (tail_bytes) HIP_TRY(hipMemcpyAsync(c.b_aux.p, tails, tail_bytes, hipMemcpyHostToDevice, c.stream));
+    int rc = launch_deal_ct(c, (const uint8_t*)c.b_pk.p, (const uint8_t*)c.b_aux.p, n_val, total, threshold,
+                            (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p, nullptr, nullptr, c.stream);
+    if (rc) return rc;
+    rc = launch_commit_ct(c, (const uint8_t*)c.b_pk.p, (const uint8_t*)c.b_aux.p, n_val, threshold,
+                          (uint8_t*)c.dl_pub.p, (int32_t*)c.dl_pst.p, c.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_shares, c.b_out.p, share_bytes, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_val * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(out_com, c.dl_pub.p, n_com * 48, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(com_status, c.dl_pst.p, n_com * 4, hipMemcpyDeviceToHost, c.stream));
+    return HIPBLS_OK;
+  };
+  return finish_wiped(c, body(), {{c.b_pk.p, n_val * 32}, {c.b_aux.p, tail_bytes}, {c.b_out.p, share_bytes}});
+}
+
+int share_check_host(Context& c, const uint8_t* shares, const uint8_t* commitments, uint64_t n_val, uint32_t n_dealers,
+                     uint32_t threshold, int64_t my_id, int32_t* status) {
+  const uint64_t n = n_val * n_dealers, com_bytes = n * threshold * 48;
+  HIP_TRY(c.b_aux.ensure(n * 32));
+  HIP_TRY(c.b_pk.ensure(com_bytes));
+  HIP_TRY(c.b_st.ensure(n * 4));
+  auto body = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(c.b_aux.p, shares, n * 32, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.b_pk.p, commitments, com_bytes, hipMemcpyHostToDevice, c.stream));
+    const int rc = launch_share_check(c, (const uint8_t*)c.b_aux.p, (const uint8_t*)c.b_pk.p, n, threshold, my_id,
+                                      (int32_t*)c.b_st.p, c.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+    return HIPBLS_OK;
+  };
+  return finish_wiped(c, body(), {{c.b_aux.p, n * 32}});
+}
+
+int share_sum_host(Context& c, const uint8_t* shares, const uint8_t* include, uint64_t n_val, uint32_t n_dealers,
+                   uint8_t* out_shares, int32_t* status, uint8_t* out_pubs, int32_t* pub_status) {
+  const uint64_t n = n_val * n_dealers;
+  HIP_TRY(c.b_aux.ensure(n * 32));
+  if (include) HIP_TRY(c.b_ids.ensure(n));
+  HIP_TRY(c.b_out.ensure(n_val * 32));
+  HIP_TRY(c.b_st.ensure(n_val * 4));
+  if (out_pubs) {
+    HIP_TRY(c.dl_pub.ensure(n_val * 48));
+    HIP_TRY(c.dl_pst.ensure(n_val * 4));
+  }
+  auto body = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(c.b_aux.p, shares, n * 32, hipMemcpyHostToDevice, c.stream));
+    if (include) HIP_TRY(hipMemcpyAsync(c.b_ids.p, include, n, hipMemcpyHostToDevice, c.stream));
+    const int rc = launch_share_sum(c, (const uint8_t*)c.b_aux.p, include ? (const uint8_t*)c.b_ids.p : nullptr, n_val,
+                                    n_dealers, (uint8_t*)c.b_out.p, (int32_t*)c.b_st.p,
+                                    out_pubs ? (uint8_t*)c.dl_pub.p : nullptr,
+                                    out_pubs ? (int32_t*)c.dl_pst.p : nullptr, c.stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_shares, c.b_out.p, n_val * 32, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(status, c.b_st.p, n_val * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out_pubs) {
+      HIP_TRY(hipMemcpyAsync(out_pubs, c.dl_pub.p, n_val * 48, hipMemcpyDeviceToHost, c.stream));
+      HIP_TRY(hipMemcpyAsync(pub_status, c.dl_pst.p, n_val * 4, hipMemcpyDeviceToHost, c.stream));
+    }
+    return HIPBLS_OK;
+  };
+  return finish_wiped(c, body(), {{c.b_aux.p, n * 32}, {c.b_out.p, n_val * 32}});
+}
+
 int fav_host(Context& c, const uint8_t* pks, const uint64_t* koffs, uint64_t n_groups, const uint8_t* sigs,
              const uint8_t* msgs, const uint64_t* moffs, int32_t* status) {
   const uint64_t nkeys = koffs[n_groups], msg_total = moffs[n_groups];
@@ -4673,6 +4839,121 @@ int hipbls_public_key_share_batch_device(const uint8_t* d_commitments, uint64_t 
   ENTER_CTX(c);
   ON_STREAM(c, stream, s);
   return launch_pk_share(c, d_commitments, n_val, n_dealers, threshold, d_ids, n_ids, d_out_pubs, d_status, s);
+}
+
+// A joint-Feldman dealing round in batches: the argument rules of the split and of the share call.
+bool deal_commit_args_ok(const void* secrets, const void* tails, uint64_t n_val, uint32_t total, uint32_t threshold,
+                         const void* out_shares, const void* status, const void* out_com, const void* com_status) {
+  if (!out_com || !com_status || threshold > kVssMaxThreshold) return false;
+  if (!deal_args_ok(secrets, tails, n_val, total, threshold, out_shares, status, nullptr, nullptr)) return false;
+  return n_val < kDealMaxLanes && n_val * threshold < kDealMaxLanes;  // factors below 2^31: no overflow
+}
+
+constexpr uint64_t kSplitDkg = 1024;  // share-check and share-sum lanes per context range
+
+// n_val n_dealers (the lanes) and, with threshold, the commitments below 2^31
+bool dkg_lanes_ok(uint64_t n_val, uint32_t n_dealers, uint64_t threshold) {
+  if (n_val >= kDealMaxLanes || n_dealers >= kDealMaxLanes || threshold > kVssMaxThreshold) return false;
+  const uint64_t n = n_val * n_dealers;  // below 2^62
+  return n < kDealMaxLanes && n * threshold < kDealMaxLanes;
+}
+
+int hipbls_deal_commit_batch_ct(const uint8_t* secrets, const uint8_t* poly_tails, uint64_t n_val, uint32_t total,
+                                uint32_t threshold, uint8_t* out_shares, int32_t* status, uint8_t* out_commitments,
+                                int32_t* com_status) {
+  if (threshold == 0 || total == 0) return arg_err("bad deal arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!deal_commit_args_ok(secrets, poly_tails, n_val, total, threshold, out_shares, status, out_commitments, com_status))
+    return arg_err("bad deal arguments");
+  ENSURE_INIT();
+  const uint64_t lanes = std::max<uint64_t>((uint64_t)total + 1, threshold), per = kSplitDeal / lanes;
+  const uint64_t tail = 32 * (uint64_t)(threshold - 1);
+  return run_ranges(plan_ranges(n_val, parts_for(n_val, per ? per : 1), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      return deal_commit_host(c, secrets + 32 * lo, poly_tails ? poly_tails + tail * lo : poly_tails,
+                                              hi - lo, total, threshold, out_shares + 32 * (uint64_t)total * lo,
+                                              status + lo, out_commitments + 48 * (uint64_t)threshold * lo,
+                                              com_status + (uint64_t)threshold * lo);
+                    });
+}
+
+int hipbls_deal_commit_batch_ct_device(const uint8_t* d_secrets, const uint8_t* d_poly_tails, uint64_t n_val,
+                                       uint32_t total, uint32_t threshold, uint8_t* d_out_shares, int32_t* d_status,
+                                       uint8_t* d_out_commitments, int32_t* d_com_status, void* stream) {
+  if (threshold == 0 || total == 0) return arg_err("bad deal arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!deal_commit_args_ok(d_secrets, d_poly_tails, n_val, total, threshold, d_out_shares, d_status, d_out_commitments,
+                           d_com_status))
+    return arg_err("bad deal arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  const int rc = launch_deal_ct(c, d_secrets, d_poly_tails, n_val, total, threshold, d_out_shares, d_status, nullptr,
+                                nullptr, s);
+  if (rc) return rc;
+  return launch_commit_ct(c, d_secrets, d_poly_tails, n_val, threshold, d_out_commitments, d_com_status, s);
+}
+
+int hipbls_verify_secret_shares_batch_ct(const uint8_t* shares, const uint8_t* commitments, uint64_t n_val,
+                                         uint32_t n_dealers, uint32_t threshold, int64_t my_id, int32_t* status) {
+  if (threshold == 0 || n_dealers == 0) return arg_err("bad share check arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!shares || !commitments || !status || !dkg_lanes_ok(n_val, n_dealers, threshold))
+    return arg_err("bad share check arguments");
+  ENSURE_INIT();
+  const uint64_t per = kSplitDkg / n_dealers, com_row = 48 * (uint64_t)n_dealers * threshold;
+  return run_ranges(plan_ranges(n_val, parts_for(n_val, per ? per : 1), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      return share_check_host(c, shares + 32 * (uint64_t)n_dealers * lo, commitments + com_row * lo,
+                                              hi - lo, n_dealers, threshold, my_id, status + (uint64_t)n_dealers * lo);
+                    });
+}
+
+int hipbls_verify_secret_shares_batch_ct_device(const uint8_t* d_shares, const uint8_t* d_commitments, uint64_t n_val,
+                                                uint32_t n_dealers, uint32_t threshold, int64_t my_id,
+                                                int32_t* d_status, void* stream) {
+  if (threshold == 0 || n_dealers == 0) return arg_err("bad share check arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!d_shares || !d_commitments || !d_status || !dkg_lanes_ok(n_val, n_dealers, threshold))
+    return arg_err("bad share check arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_share_check(c, d_shares, d_commitments, n_val * n_dealers, threshold, my_id, d_status, s);
+}
+
+int hipbls_combine_shares_batch_ct(const uint8_t* shares, const uint8_t* include, uint64_t n_val, uint32_t n_dealers,
+                                   uint8_t* out_shares, int32_t* status, uint8_t* out_pubs, int32_t* pub_status) {
+  if (n_dealers == 0) return arg_err("bad combine arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!shares || !out_shares || !status || (out_pubs == nullptr) != (pub_status == nullptr) ||
+      !dkg_lanes_ok(n_val, n_dealers, 1))
+    return arg_err("bad combine arguments");
+  ENSURE_INIT();
+  return run_ranges(plan_ranges(n_val, parts_for(n_val, kSplitDkg), nullptr),
+                    [&](Context& c, uint64_t lo, uint64_t hi) {
+                      return share_sum_host(c, shares + 32 * (uint64_t)n_dealers * lo,
+                                            include ? include + (uint64_t)n_dealers * lo : include, hi - lo, n_dealers,
+                                            out_shares + 32 * lo, status + lo, out_pubs ? out_pubs + 48 * lo : out_pubs,
+                                            pub_status ? pub_status + lo : pub_status);
+                    });
+}
+
+int hipbls_combine_shares_batch_ct_device(const uint8_t* d_shares, const uint8_t* d_include, uint64_t n_val,
+                                          uint32_t n_dealers, uint8_t* d_out_shares, int32_t* d_status,
+                                          uint8_t* d_out_pubs, int32_t* d_pub_status, void* stream) {
+  if (n_dealers == 0) return arg_err("bad combine arguments");
+  if (n_val == 0) return HIPBLS_OK;
+  if (!d_shares || !d_out_shares || !d_status || (d_out_pubs == nullptr) != (d_pub_status == nullptr) ||
+      !dkg_lanes_ok(n_val, n_dealers, 1))
+    return arg_err("bad combine arguments");
+  ENSURE_INIT();
+  Context& c = ctx_of(d_status);
+  ENTER_CTX(c);
+  ON_STREAM(c, stream, s);
+  return launch_share_sum(c, d_shares, d_include, n_val, n_dealers, d_out_shares, d_status, d_out_pubs, d_pub_status, s);
 }
 
 int hipbls_public_key_recover_batch(const uint8_t* pubshares, const int64_t* ids, const uint64_t* group_offsets,

@@ -133,6 +133,16 @@ def load_library(path: str = _LIB_PATH) -> ctypes.CDLL:
         "hipbls_public_key_share_batch_device": ([vp, u64, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp,
                                                   vp], ctypes.c_int),
         "hipbls_public_key_recover_batch_device": ([vp, vp, vp, u64, u64, vp, vp, vp], ctypes.c_int),
+        "hipbls_deal_commit_batch_ct": ([u8p, u8p, u64, ctypes.c_uint32, ctypes.c_uint32, u8p, i32p, u8p, i32p],
+                                        ctypes.c_int),
+        "hipbls_verify_secret_shares_batch_ct": ([u8p, u8p, u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, i32p],
+                                                 ctypes.c_int),
+        "hipbls_combine_shares_batch_ct": ([u8p, u8p, u64, ctypes.c_uint32, u8p, i32p, u8p, i32p], ctypes.c_int),
+        "hipbls_deal_commit_batch_ct_device": ([vp, vp, u64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp],
+                                               ctypes.c_int),
+        "hipbls_verify_secret_shares_batch_ct_device": ([vp, vp, u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64,
+                                                         vp, vp], ctypes.c_int),
+        "hipbls_combine_shares_batch_ct_device": ([vp, vp, u64, ctypes.c_uint32, vp, vp, vp, vp, vp], ctypes.c_int),
         "hipbls_batch_verify_rlc": ([u8p, u8p, u32p, u64, u8p, u64p, u64, u8p, i32p], ctypes.c_int),
         "hipbls_batch_verify_rlc_device": ([vp, vp, vp, u64, vp, vp, u64, u8p, vp, vp], ctypes.c_int),
         "hipbls_rlc_stats": ([u64p, u64p, u64p], ctypes.c_int),
@@ -195,6 +205,9 @@ def exported_symbols() -> List[str]:
         "hipbls_sigcache_config", "hipbls_sigcache_stats",
         "hipbls_public_key_share_batch", "hipbls_public_key_recover_batch",
         "hipbls_public_key_share_batch_device", "hipbls_public_key_recover_batch_device",
+        "hipbls_deal_commit_batch_ct", "hipbls_verify_secret_shares_batch_ct", "hipbls_combine_shares_batch_ct",
+        "hipbls_deal_commit_batch_ct_device", "hipbls_verify_secret_shares_batch_ct_device",
+        "hipbls_combine_shares_batch_ct_device",
     ]
 
 
@@ -441,6 +454,97 @@ class HipBLS:
         pks, st = self.secret_to_public_key_batch_ct(shares)
         want, wst = self.public_key_share_batch([[list(c)] for c in commitments], [my_id])
         return [st[d] == OK and wst[d] == OK and pks[d] == want[d][0] for d in range(len(shares))]
+
+    # ---------------------------------------------------------------- a joint-Feldman dealing round in batches
+    def deal_commit_batch_ct(self, secrets_: Sequence[bytes], tails: Sequence[Sequence[bytes]], total: int,
+                             threshold: int):
+        """A dealer's round 1 for many validators in one call (hipbls_deal_commit_batch_ct): the shares of
+        threshold_split_batch_ct and the Feldman commitments to every coefficient, on the secret-independent kernels.
+        Returns (shares, status, commitments, com_status): shares and status as threshold_split_batch_ct;
+        commitments[v][j] = [a_j] g1 compressed (a_0 the secret), the infinity encoding with OK for a zero
+        coefficient, zero bytes and ERR_SECRET for every coefficient of a validator whose status is ERR_SECRET.
+        commitments[v] is one dealer's polynomial as public_key_share_batch reads it."""
+        n = len(secrets_)
+        if len(tails) != n:
+            raise ValueError("one polynomial tail per secret")
+        _check_lengths("secret keys", secrets_, 32)
+        for t in tails:
+            if len(t) != max(threshold, 1) - 1:
+                raise ValueError("a polynomial tail has threshold - 1 coefficients")
+            _check_lengths("polynomial coefficients", t, 32)
+        out = ctypes.create_string_buffer(32 * max(n * total, 1))
+        st = _status_array(n)
+        com = ctypes.create_string_buffer(48 * max(n * threshold, 1))
+        cst = _status_array(n * threshold)
+        _check(self.lib.hipbls_deal_commit_batch_ct(b"".join(secrets_), b"".join(b"".join(t) for t in tails), n, total,
+                                                    threshold, out, st, com, cst), self.lib)
+        raw, craw, clist = out.raw, com.raw, list(cst)
+        t = threshold
+        return ([{i + 1: raw[32 * (total * v + i):32 * (total * v + i) + 32] for i in range(total)} for v in range(n)],
+                list(st)[:n],
+                [[craw[48 * (t * v + j):48 * (t * v + j) + 48] for j in range(t)] for v in range(n)],
+                [clist[t * v:t * v + t] for v in range(n)])
+
+    def verify_secret_shares_batch_ct(self, shares: Sequence[Sequence[bytes]],
+                                      commitments: Sequence[Sequence[Sequence[bytes]]], my_id: int) -> List[List[int]]:
+        """A receiver's round 2 check for many validators in one call (hipbls_verify_secret_shares_batch_ct):
+        shares[v][d] is what dealer d sent this node (operator id my_id) for validator v, commitments[v][d] that
+        dealer's commitments.  Returns status[v][d]: ERR_PUBKEY (a commitment does not decode), ERR_SECRET (the share
+        >= r), ERR_VERIFY ([share] g1 is not the dealer's public polynomial at my_id) or OK.  The comparison is made
+        on the device; only the verdicts come back."""
+        n = len(shares)
+        if len(commitments) != n:
+            raise ValueError("one commitment list per share")
+        n_dealers = len(shares[0]) if n else 1
+        threshold = len(commitments[0][0]) if n and n_dealers else 1
+        flat_s, flat_c = [], []
+        for row, val in zip(shares, commitments):
+            if len(row) != n_dealers or len(val) != n_dealers:
+                raise ValueError("every validator has the same number of dealers")
+            flat_s.extend(row)
+            for poly in val:
+                if len(poly) != threshold:
+                    raise ValueError("every polynomial has threshold commitments")
+                flat_c.extend(poly)
+        _check_lengths("shares", flat_s, 32)
+        _check_lengths("commitments", flat_c, 48)
+        st = _status_array(n * n_dealers)
+        _check(self.lib.hipbls_verify_secret_shares_batch_ct(b"".join(flat_s), b"".join(flat_c), n, n_dealers,
+                                                             threshold, _go_int(my_id), st), self.lib)
+        slist = list(st)
+        return [slist[n_dealers * v:n_dealers * v + n_dealers] for v in range(n)]
+
+    def combine_shares_batch_ct(self, shares: Sequence[Sequence[bytes]],
+                                include: Optional[Sequence[Sequence[bool]]] = None, with_pubs: bool = True):
+        """The last step of a joint dealing for many validators in one call (hipbls_combine_shares_batch_ct): this
+        node's final share of validator v is the sum of shares[v][d] over the dealers with include[v][d] (None: all).
+        Returns (out_shares, status, pubs, pub_status): status[v] ERR_COMBINE (no dealer included), ERR_SECRET (an
+        included share >= r) or OK, zero bytes unless OK; with with_pubs the pubshare [out_share] g1 and its status as
+        secret_to_public_key_batch_ct gives it, else None for both."""
+        n = len(shares)
+        n_dealers = len(shares[0]) if n else 1
+        flat = []
+        for row in shares:
+            if len(row) != n_dealers:
+                raise ValueError("every validator has the same number of dealers")
+            flat.extend(row)
+        _check_lengths("shares", flat, 32)
+        inc = None
+        if include is not None:
+            if len(include) != n or any(len(r) != n_dealers for r in include):
+                raise ValueError("one include flag per share")
+            inc = bytes(1 if f else 0 for r in include for f in r)
+        out = ctypes.create_string_buffer(32 * max(n, 1))
+        st = _status_array(n)
+        pubs = ctypes.create_string_buffer(48 * max(n, 1)) if with_pubs else None
+        pst = _status_array(n) if with_pubs else None
+        _check(self.lib.hipbls_combine_shares_batch_ct(b"".join(flat), inc, n, n_dealers, out, st, pubs, pst), self.lib)
+        raw = out.raw
+        outs = [raw[32 * v:32 * v + 32] for v in range(n)]
+        if not with_pubs:
+            return outs, list(st)[:n], None, None
+        praw = pubs.raw
+        return outs, list(st)[:n], [praw[48 * v:48 * v + 48] for v in range(n)], list(pst)[:n]
 
     def verify_pubshares(self, pubkey: bytes, pubshares: Mapping[int, bytes], threshold: int) -> bool:
         """Whether every pubshare lies on the one polynomial of degree threshold - 1 through pubkey (its value at 0).

@@ -324,6 +324,51 @@ int hipbls_public_key_share_batch(const uint8_t* commitments, uint64_t n_val, ui
 int hipbls_public_key_recover_batch(const uint8_t* pubshares, const int64_t* ids, const uint64_t* group_offsets,
                                     uint64_t n_groups, uint8_t* out_pubkeys, int32_t* status);
 
+/* One round of a joint-Feldman dealing in batches over all validators of a ceremony, secret-independent as the split
+ * above: a dealer's shares with their Feldman commitments, a receiver's check of the shares it was
+ * sent, and the sum of the qualified dealers' shares.
+ *
+ * hipbls_deal_commit_batch_ct: inputs, out_shares and status exactly as hipbls_threshold_split_batch_ct (its kernel,
+ * timed as deal_ct, without public keys), then one lane per (v, j), j = 0..threshold-1 (timed as commit_ct):
+ * out_commitments[48 (v threshold + j) ..] = [a_j] g1 compressed, a_0 the secret, a_j = poly_tails' coefficient j-1,
+ * by 64 mixed additions over the context's comb: the layout hipbls_public_key_share_batch reads with n_dealers = 1.
+ * com_status[v threshold + j] = OK | ERR_SECRET.  A zero coefficient gives the infinity encoding (0xc0 then 47 zero
+ * bytes) with status OK (a legal dealing, as the share call reads it); a validator whose status[v] is ERR_SECRET gives
+ * zero bytes and ERR_SECRET for all its commitments.  n_val == 0 is OK; HIPBLS_ERR_ARG as the split, and for a null
+ * out_commitments or com_status, threshold > 65,535 or n_val threshold >= 2^31.  Validators are split over the
+ * contexts whole; the device copies of secrets, tails and shares are zeroed on the call's stream before the call
+ * returns. */
+int hipbls_deal_commit_batch_ct(const uint8_t* secrets, const uint8_t* poly_tails, uint64_t n_val, uint32_t total,
+                                uint32_t threshold, uint8_t* out_shares, int32_t* status, uint8_t* out_commitments,
+                                int32_t* com_status);
+
+/* The receiver's check.  shares[32 (v n_dealers + d) ..] is the share dealer d sent for validator v; commitments in
+ * hipbls_public_key_share_batch's layout, C[v][d][j] = commitments[48 ((v n_dealers + d) threshold + j) ..].
+ * status[v n_dealers + d], decided in this order: ERR_PUBKEY (a commitment of (v, d) does not decode: public),
+ * ERR_SECRET (the share >= r), ERR_VERIFY ([share] g1 != sum_j [my_id^j] C[v][d][j]), OK.  The verdict is public (a
+ * complaint is broadcast); nothing else about a share steers control flow or addresses.  A zero share is compared as
+ * the infinity encoding, not rejected.  my_id follows the share call's rule for ids: negative values and INT64_MIN
+ * work, and 0 evaluates at C[v][d][0].  Kernels: each (v, d) as a one-dealer validator of the share call evaluated at
+ * my_id (g1_decode, vss_eval), then one lane per (v, d) on the same stream (share_check_ct): [share] g1 over the comb,
+ * compressed, and compared with the expected 48 bytes on the device by an OR of XORs.  n_val == 0 is OK;
+ * HIPBLS_ERR_ARG: threshold == 0, n_dealers == 0, a null pointer with a non-zero count, threshold > 65,535, or n_val,
+ * n_val n_dealers or n_val n_dealers threshold >= 2^31.  Validators are split over the contexts whole; the device copy
+ * of the shares is zeroed before the call returns. */
+int hipbls_verify_secret_shares_batch_ct(const uint8_t* shares, const uint8_t* commitments, uint64_t n_val,
+                                         uint32_t n_dealers, uint32_t threshold, int64_t my_id, int32_t* status);
+
+/* A node's final share: out_shares[32 v ..] = sum over d of include[v n_dealers + d] ? shares[32 (v n_dealers + d) ..]
+ * : 0, mod r.  include: one byte per (v, d), non-zero = the dealer is qualified (public); null = every dealer.
+ * status[v] = ERR_COMBINE (no dealer included: public, decided first) | ERR_SECRET (an included share >= r) | OK;
+ * zero bytes on error.  An excluded dealer's share is not looked at: it may be >= r.
+ * out_pubs / pub_status (both null or both given): [out_share_v] g1 with hipbls_secret_to_public_key_batch_ct's bytes
+ * and status (ERR_SECRET and zero bytes for a zero sum or a validator that failed).  One kernel, one lane per
+ * validator (share_sum_ct).  n_val == 0 is OK; HIPBLS_ERR_ARG: n_dealers == 0, a null pointer with a non-zero count,
+ * only one of out_pubs / pub_status, or n_val or n_val n_dealers >= 2^31.  Validators are split over the contexts
+ * whole; the device copies of the shares and of the sums are zeroed before the call returns. */
+int hipbls_combine_shares_batch_ct(const uint8_t* shares, const uint8_t* include, uint64_t n_val, uint32_t n_dealers,
+                                   uint8_t* out_shares, int32_t* status, uint8_t* out_pubs, int32_t* pub_status);
+
 /* Random-linear-combination BatchVerify.  Item i is (pks[48 i..], message msg_idx[i], sigs[96 i..]);
  * message m is msgs[msg_offsets[m] .. msg_offsets[m+1]) (n_msgs distinct messages, each hashed once).
  * status[i] is exactly hipbls_verify_batch's (i.e. tbls.Verify's) outcome for the item: items are
@@ -542,6 +587,20 @@ int hipbls_public_key_share_batch_device(const uint8_t* d_commitments, uint64_t 
 int hipbls_public_key_recover_batch_device(const uint8_t* d_pubshares, const int64_t* d_ids,
                                            const uint64_t* d_group_offsets, uint64_t n_groups, uint64_t n_parts,
                                            uint8_t* d_out_pubkeys, int32_t* d_status, void* stream);
+/* As hipbls_deal_commit_batch_ct / hipbls_verify_secret_shares_batch_ct / hipbls_combine_shares_batch_ct on device
+ * buffers: they only enqueue (on the context that owns d_status; the first call on a context also enqueues the build
+ * of its comb table), with the same argument rules.  my_id is passed by value.  The share check keeps the expected
+ * bytes in the context's workspace, ordered against calls on other streams.  The secrets stay in the caller's
+ * buffers; clearing them is the caller's. */
+int hipbls_deal_commit_batch_ct_device(const uint8_t* d_secrets, const uint8_t* d_poly_tails, uint64_t n_val,
+                                       uint32_t total, uint32_t threshold, uint8_t* d_out_shares, int32_t* d_status,
+                                       uint8_t* d_out_commitments, int32_t* d_com_status, void* stream);
+int hipbls_verify_secret_shares_batch_ct_device(const uint8_t* d_shares, const uint8_t* d_commitments, uint64_t n_val,
+                                                uint32_t n_dealers, uint32_t threshold, int64_t my_id,
+                                                int32_t* d_status, void* stream);
+int hipbls_combine_shares_batch_ct_device(const uint8_t* d_shares, const uint8_t* d_include, uint64_t n_val,
+                                          uint32_t n_dealers, uint8_t* d_out_shares, int32_t* d_status,
+                                          uint8_t* d_out_pubs, int32_t* d_pub_status, void* stream);
 
 /* As hipbls_batch_verify_rlc; seed32 is a host pointer.  An out-of-range msg_idx[i] yields
  * status[i] = HIPBLS_ERR_ARG. */

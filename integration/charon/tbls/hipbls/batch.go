@@ -578,3 +578,181 @@ func (h HipBLS) VerifyPubShares(pubkey tbls.PublicKey, pubshares map[int]tbls.Pu
 
 	return true, nil
 }
+
+// DealtCommitted is one validator's result of DealWithCommitments: the shares f(i), i = 1..total, and the Feldman
+// commitments [a_j] g1 to the coefficients of f, j = 0..threshold-1 (Commitments[0] is the dealer's public key for
+// this validator).
+type DealtCommitted struct {
+	Shares      map[int]tbls.PrivateKey
+	Commitments []tbls.PublicKey
+}
+
+// DealWithCommitments is a dealer's round 1 of a joint-Feldman dealing for every validator in one call: what
+// dkg/frost.go:117-149 does validator by validator in kryptology (the shares for every operator and the commitments to
+// broadcast), on kernels whose instruction stream and memory addresses do not depend on the secrets
+// (hipbls_deal_commit_batch_ct).  The polynomial tails come from crypto/rand as ThresholdSplit's do.  errs[v] is set
+// when the secret of validator v is not a scalar.  Not a method of tbls.Implementation.
+func (h HipBLS) DealWithCommitments(secrets []tbls.PrivateKey, total, threshold uint) ([]DealtCommitted, []error, error) {
+	n := len(secrets)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	flat := make([]byte, 0, 32*n)
+	poly := make([]byte, 0, 32*n*int(threshold))
+	for _, s := range secrets {
+		flat = append(flat, s[:]...)
+		for i := 1; i < int(threshold); i++ {
+			k, err := h.GenerateSecretKey()
+			if err != nil {
+				return nil, nil, err
+			}
+			poly = append(poly, k[:]...)
+		}
+	}
+	shares := make([]byte, 32*n*int(total))
+	coms := make([]byte, 48*n*int(threshold))
+	status := make([]int32, n)
+	comStatus := make([]int32, n*int(threshold))
+	if rc := C.hipbls_deal_commit_batch_ct(u8(flat), u8(poly), C.uint64_t(n), C.uint32_t(total), C.uint32_t(threshold),
+		u8(shares), i32(status), u8(coms), i32(comStatus)); rc != C.HIPBLS_OK {
+		return nil, nil, observeFailure("deal_commit", n, devErr(rc))
+	}
+	out := make([]DealtCommitted, n)
+	errs := make([]error, n)
+	for v := range secrets {
+		if status[v] != C.HIPBLS_OK {
+			errs[v] = errors.New("cannot unmarshal bytes into Herumi secret key")
+			continue
+		}
+		d := DealtCommitted{Shares: make(map[int]tbls.PrivateKey, total), Commitments: make([]tbls.PublicKey, threshold)}
+		for k := 1; k <= int(total); k++ {
+			var sk tbls.PrivateKey
+			copy(sk[:], shares[32*(v*int(total)+k-1):])
+			d.Shares[k] = sk
+		}
+		for j := range d.Commitments {
+			copy(d.Commitments[j][:], coms[48*(v*int(threshold)+j):])
+		}
+		out[v] = d
+	}
+	observe("deal_commit", errs)
+
+	return out, errs, nil
+}
+
+// VerifySecretSharesBatch is a receiver's round 2 check for every validator in one call (dkg/frost.go:198-248;
+// hipbls_verify_secret_shares_batch_ct): shares[v][d] is what dealer d sent this node (operator index myID) for
+// validator v, commitments[v][d] that dealer's commitments.  errs[v][d] is nil when [shares[v][d]] g1 equals the
+// dealer's public polynomial at myID; the comparison is made on the device and only the verdicts come back.  Not a
+// method of tbls.Implementation.
+func (HipBLS) VerifySecretSharesBatch(shares [][]tbls.PrivateKey, commitments [][][]tbls.PublicKey, myID int) ([][]error, error) {
+	n := len(shares)
+	if n != len(commitments) {
+		return nil, errors.New("one commitment list per share")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	dealers := len(shares[0])
+	if dealers == 0 || len(commitments[0]) != dealers || len(commitments[0][0]) == 0 {
+		return nil, errors.New("share checks need a dealer and a commitment")
+	}
+	threshold := len(commitments[0][0])
+	flat := make([]byte, 0, 32*n*dealers)
+	coms := make([]byte, 0, 48*n*dealers*threshold)
+	for v := range shares {
+		if len(shares[v]) != dealers || len(commitments[v]) != dealers {
+			return nil, errors.New("every validator has the same number of dealers")
+		}
+		for d := range shares[v] {
+			flat = append(flat, shares[v][d][:]...)
+			if len(commitments[v][d]) != threshold {
+				return nil, errors.New("every polynomial has threshold commitments")
+			}
+			for _, c := range commitments[v][d] {
+				coms = append(coms, c[:]...)
+			}
+		}
+	}
+	status := make([]int32, n*dealers)
+	if rc := C.hipbls_verify_secret_shares_batch_ct(u8(flat), u8(coms), C.uint64_t(n), C.uint32_t(dealers),
+		C.uint32_t(threshold), C.int64_t(myID), i32(status)); rc != C.HIPBLS_OK {
+		return nil, observeFailure("verify_secret_shares", n*dealers, devErr(rc))
+	}
+	out := make([][]error, n)
+	all := make([]error, 0, n*dealers)
+	for v := range shares {
+		out[v] = make([]error, dealers)
+		for d := range out[v] {
+			switch status[v*dealers+d] {
+			case C.HIPBLS_OK:
+			case C.HIPBLS_ERR_PUBKEY:
+				out[v][d] = errors.New("cannot set compressed public key in Herumi format")
+			case C.HIPBLS_ERR_SECRET:
+				out[v][d] = errors.New("cannot unmarshal bytes into Herumi secret key")
+			default:
+				out[v][d] = errors.New("secret share does not match the dealer's commitments")
+			}
+			all = append(all, out[v][d])
+		}
+	}
+	observe("verify_secret_shares", all)
+
+	return out, nil
+}
+
+// CombineShares is the last step of a joint dealing for every validator in one call
+// (hipbls_combine_shares_batch_ct): this node's final share of validator v is the sum of shares[v][d] over the dealers
+// with include[v][d] (a nil include takes every dealer), and its pubshare follows from it, with no secret passing
+// through host integers.  errs[v] is set when no dealer is included, an included share is not a scalar, or the sum is
+// zero (a secret without a public key).  Not a method of tbls.Implementation.
+func (HipBLS) CombineShares(shares [][]tbls.PrivateKey, include [][]bool) ([]tbls.PrivateKey, []tbls.PublicKey, []error, error) {
+	n := len(shares)
+	if n == 0 {
+		return nil, nil, nil, nil
+	}
+	dealers := len(shares[0])
+	if dealers == 0 || (include != nil && len(include) != n) {
+		return nil, nil, nil, errors.New("combining shares needs a dealer and one include flag per share")
+	}
+	flat := make([]byte, 0, 32*n*dealers)
+	var mask []byte
+	for v := range shares {
+		if len(shares[v]) != dealers || (include != nil && len(include[v]) != dealers) {
+			return nil, nil, nil, errors.New("every validator has the same number of dealers")
+		}
+		for d := range shares[v] {
+			flat = append(flat, shares[v][d][:]...)
+			if include != nil {
+				var b byte
+				if include[v][d] {
+					b = 1
+				}
+				mask = append(mask, b)
+			}
+		}
+	}
+	sums := make([]tbls.PrivateKey, n)
+	pubs := make([]tbls.PublicKey, n)
+	status := make([]int32, n)
+	pubStatus := make([]int32, n)
+	if rc := C.hipbls_combine_shares_batch_ct(u8(flat), u8(mask), C.uint64_t(n), C.uint32_t(dealers),
+		(*C.uint8_t)(unsafe.Pointer(&sums[0][0])), i32(status), (*C.uint8_t)(unsafe.Pointer(&pubs[0][0])),
+		i32(pubStatus)); rc != C.HIPBLS_OK {
+		return nil, nil, nil, observeFailure("combine_shares", n, devErr(rc))
+	}
+	errs := make([]error, n)
+	for v := range shares {
+		switch {
+		case status[v] == C.HIPBLS_ERR_SECRET:
+			errs[v] = errors.New("cannot unmarshal bytes into Herumi secret key")
+		case status[v] != C.HIPBLS_OK:
+			errs[v] = errors.New("no qualified dealer to combine shares from")
+		case pubStatus[v] != C.HIPBLS_OK:
+			errs[v] = errors.New("cannot obtain public key from secret")
+		}
+	}
+	observe("combine_shares", errs)
+
+	return sums, pubs, errs, nil
+}
